@@ -6,6 +6,19 @@ model in the reference's operand width (x6: every fp32 operand split exactly int
 fp32 accumulation), synthetic white-noise clips already resident in HBM, random (counter-hash) weights.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--precision h3|x6|fp32|bf16]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it builds the model, warms up, times the K steps, writes the
+last timed step's outputs when --dump-outputs is given, and prints the result line (roofline, cpu_baseline, parity
+and h3 are null in it).  --full adds everything else described below: the per-kernel HIP-event timing inside the
+timed region and the roofline drawn from it, the MFMA probe, the CPU oracle baseline, the index / waveform parity
+legs and, for config 2, the h3 leg.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its LAST timed step as
+DIR/<name>.npy in float32 (codes: the index tensor; vq_post: the quantised latent handed back beside it; wav: the
+decoded waveforms), at most 64 MB in all: an array over its share is stored as a fixed seeded sample of its
+elements (sample_positions: the same flat positions in every run).  Inputs (counter-hash clips and weights,
+seeded tokens) are the same in every run with the same arguments.
 
 --gpus N > 1 starts N ranks itself (python -m torch.distributed.run as a child process, before this
 process touches the GPU); under torchrun WORLD_SIZE must equal --gpus.  One process per GPU, RCCL.
@@ -22,10 +35,10 @@ process touches the GPU); under torchrun WORLD_SIZE must equal --gpus.  One proc
 
 A step = one batch per GPU through the path; for N > 1 each step ends with the RCCL all-gather of the
 batch's index tensor (clip-sharded data parallelism, weak scaling).  Rank 0 prints one JSON line with
-the whole-job throughput (audio-seconds per second, all GPUs), the roofline of the dominant kernel
-(HIP-event timed inside the timed region), the CPU oracle baseline, the index parity of rank 0's batch
-against the reference's full-size fixture (tests/golden/full_config2_default.npz: every mismatch with
-its fp64 top-2 gap) and, for config 2, the same workload in the opt-in h3 arithmetic (22-bit operands:
+the whole-job throughput (audio-seconds per second, all GPUs) and ms_per_step and, with --full, the
+roofline of the dominant kernel (HIP-event timed inside the timed region), the CPU oracle baseline,
+the index parity of rank 0's batch against the reference's full-size fixture
+(tests/golden/full_config2_default.npz: every mismatch with its fp64 top-2 gap) and, for config 2, the same workload in the opt-in h3 arithmetic (22-bit operands:
 narrower than the reference's fp32, reported as an extra leg only) beside the x6 headline.
 """
 from __future__ import annotations
@@ -166,6 +179,11 @@ def parse():
     p.add_argument("--batch", type=int, default=None, help="clips per GPU (default: the config's)")
     p.add_argument("--seconds", type=float, default=None, help="clip length (default: the config's)")
     p.add_argument("--sample-rate", type=int, default=24000)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: per-kernel timing + roofline, MFMA probe, CPU "
+                        "baseline, parity legs, the h3 leg (the --no-* switches below trim a --full run)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-kernel-timer", action="store_true")
     p.add_argument("--cpu-clips", type=int, default=4, help="clips in the CPU-baseline B=1 sample (about 3 s each)")
@@ -181,6 +199,8 @@ def parse():
     a.seconds = a.seconds or c["seconds"]
     a.precision = a.precision or c["precision"]
     a.h3_steps = a.h3_steps or a.steps  # the h3 leg is timed over as many steps as the headline
+    if not a.full:  # a plain run: the headline alone
+        a.no_cpu_baseline = a.no_kernel_timer = a.no_h3 = True
     return a
 
 
@@ -406,6 +426,40 @@ def cpu_decode_baseline(codes, sds, dk, n_clips):
             torch.cat(wavs, dim=0))
 
 
+DUMP_BUDGET = 64_000_000  # bytes of .npy files --dump-outputs may write in all
+NPY_HEADER = 1024  # allowance per file for the .npy header
+
+
+def sample_positions(numel, keep):
+    """`keep` flat positions of an array of `numel` elements: seeded, sorted, the same in every run."""
+    import numpy as np
+
+    return np.sort(np.random.default_rng(0).integers(0, numel, size=keep))
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every tensor of `outputs` ({name: tensor}) as path/<name>.npy in float32 (indices are below
+    2^24, exact), the smallest first; an array over its equal share of what is left of DUMP_BUDGET is stored as its
+    elements at sample_positions.  Returns {name: {"shape", "stored"}} for the result line."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    left, info = DUMP_BUDGET, {}
+    todo = sorted(outputs.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(todo):
+        keep = (left // (len(todo) - i) - NPY_HEADER) // 4
+        flat = t.detach().reshape(-1)
+        sampled = flat.numel() > keep
+        if sampled:
+            flat = flat[torch.from_numpy(sample_positions(flat.numel(), keep)).to(flat.device)]
+        arr = flat.float().cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), arr if sampled else arr.reshape(t.shape))
+        left -= arr.nbytes + NPY_HEADER
+        info[name] = {"shape": list(t.shape), "stored": f"sample of {arr.size}" if sampled else "all"}
+    return info
+
+
 def launch_ranks(args):
     """--gpus N > 1 without a torch.distributed environment: start N ranks as CHILD processes
     (python -m torch.distributed.run ...) before this process touches the GPU, and exit with their
@@ -457,7 +511,8 @@ def main():
     B = args.batch
     cfgn = args.config
     x = synth_batch(B, n_samples, clip0=rank * B, device=dev)  # resident in HBM before timing
-    state = {"wav": None, "host": 0}
+    state = {"wav": None, "host": 0, "post": None}
+    keep_post = args.dump_outputs is not None and rank == 0  # the quantised latent of the last step, for the dump
     tok = None
     if cfgn == 6:  # synthetic codes of the clips' frame count, uniform over the codebook, seeded per rank
         n_frames = n_samples // int(dec.hop_length)
@@ -484,6 +539,8 @@ def main():
                 state["bi"] += 1
                 return codes
             post, codes, _ = dec(enc(x), vq=True)
+            if keep_post:
+                state["post"] = post
             if cfgn == 3:
                 state["wav"] = dec(post, vq=False)
             if world > 1:
@@ -502,7 +559,8 @@ def main():
         for _ in range(n_steps):
             codes = step()
         if extractor is not None:
-            extractor.flush()  # rank 0's sink has received every timed batch (its writer thread runs behind)
+            last = extractor.flush()  # rank 0's sink has received every timed batch (its writer thread runs behind)
+            codes = codes if last is None else last  # the last timed batch's gathered codes
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -520,6 +578,15 @@ def main():
     elapsed, codes = timed(args.steps, timer)
     if cfgn == 4:
         assert extractor.stats.errors == 0 and extractor.stats.job_errors == 0, extractor.stats
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # what the last timed step handed back, before any further leg
+        outs = {"codes": codes} if codes is not None else {}
+        if state["post"] is not None:
+            outs["vq_post"] = state["post"]
+        if state["wav"] is not None:
+            outs["wav"] = state["wav"]
+        dumped = dump_outputs(args.dump_outputs, outs)
+        state["post"] = None
 
     audio_s = world * B * n_samples / args.sample_rate * args.steps
     value = audio_s / elapsed
@@ -533,7 +600,7 @@ def main():
     mine = None
     if cfgn in (2, 3):
         mine = (codes[0] if world > 1 else codes)[:, :B]
-    elif cfgn == 4:
+    elif cfgn == 4 and args.full:
         with torch.no_grad():
             mine = dec(enc(x), vq=True)[1]  # rank 0's batch 0 = clips 0..B-1 (block partition at rank 0)
 
@@ -557,7 +624,7 @@ def main():
 
     cpu = None
     parity = None
-    if rank == 0 and cfgn == 5:
+    if rank == 0 and args.full and cfgn == 5:
         # index mismatch rate of the bf16 path against the fp32-accurate path on this batch
         got = (codes[0] if world > 1 else codes)[:, :B].cpu()
         _lib.set_precision("x6")
@@ -574,7 +641,7 @@ def main():
         parity = {"clips_checked": args.cpu_clips, "samples": int(r.numel()),
                   "waveform_mse": float(((w - r) ** 2).mean()), "waveform_max_abs": float((w - r).abs().max()),
                   "note": "same codes through the CPU oracle's vq2emb + decoder"}
-    if rank == 0 and cfgn in (2, 3, 4):
+    if rank == 0 and args.full and cfgn in (2, 3, 4):
         parity = {}
         full = golden_parity(mine, args.model, n_samples, B)
         if full is not None:
@@ -606,7 +673,7 @@ def main():
         line = {
             "metric": METRIC_RT if cfgn == 3 else METRIC_DEC if cfgn == 6 else METRIC, "value": round(value, 2),
             "unit": "audio-sec/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": prec[0],
             "precision": {"mode": args.precision, "arithmetic": prec[1]}, "data": "synthetic",
@@ -619,6 +686,8 @@ def main():
             # digest the profiled bench printed here, not with whatever library the package holds when it is written
             "lib_digest": _lib.load().bc_build_digest().decode(),
         }
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if cfgn == 4:
             line["extract"] = {"batches_per_rank": args.steps, "clips_sunk_rank0": state["host"],
                                "errors": extractor.stats.job_errors}

@@ -27,6 +27,48 @@ def test_kernel_peak_by_operand_planes():
         assert abs(got - peak) < 1e-9, (name, got, peak)
 
 
+def test_plain_run_is_the_headline_alone_and_full_adds_the_rest(monkeypatch):
+    """Without --full every extra leg is off (kernel timer / roofline, CPU baseline, h3); --full turns them on and
+    the --no-* switches still trim it."""
+    import sys
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (5, 2, False, None)
+    assert a.no_cpu_baseline and a.no_kernel_timer and a.no_h3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-h3", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_h3 and not a.no_cpu_baseline and not a.no_kernel_timer
+
+
+def test_dump_outputs_float32_within_budget_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files, small arrays whole (indices exact), an array over its share as the same
+    seeded sample every time, everything within the byte budget."""
+    import os
+
+    import numpy as np
+    import torch
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 3 * bench.NPY_HEADER + 4 * (30 + 2 * 500))
+    g = torch.Generator().manual_seed(0)
+    outs = {"wav": torch.randn(7, 1, 301, generator=g), "codes": torch.randint(0, 8192, (1, 6, 5), generator=g),
+            "vq_post": torch.randn(6, 40, 5, generator=g, dtype=torch.float64)}
+    info = bench.dump_outputs(str(tmp_path / "a"), outs)
+    bench.dump_outputs(str(tmp_path / "b"), {k: outs[k] for k in ("vq_post", "codes", "wav")})
+    assert sorted(os.listdir(tmp_path / "a")) == ["codes.npy", "vq_post.npy", "wav.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= bench.DUMP_BUDGET
+    for name, t in outs.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        if info[name]["stored"] == "all":
+            assert np.array_equal(a, t.float().numpy())
+        else:
+            assert a.shape == (500,) and info[name] == {"shape": list(t.shape), "stored": "sample of 500"}
+            pos = torch.from_numpy(bench.sample_positions(t.numel(), 500))
+            assert np.array_equal(a, t.reshape(-1)[pos].float().numpy())
+    assert info["codes"]["stored"] == "all" and info["wav"]["stored"] == info["vq_post"]["stored"] == "sample of 500"
+
+
 def test_committed_pmc_summaries_are_readable(tmp_path):
     """bench.py reads the newest profiles/*pmc_traffic.json for the roofline's `traffic`: every committed summary has
     the tools/pmc_summary.py layout ({"kernels": {name: {"traffic_bytes_corrected", ...}}}); a summary is used only

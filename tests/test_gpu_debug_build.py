@@ -1,12 +1,12 @@
 """The bounds-checked debug build (include/bigcodec.h bc_debug_status) on the MI355X.
 
-audiotokenization_amd/_debug/libbigcodec_hip.so (build_lib.build(debug=True), prebuilt on the CPU like the product
-library) is loaded by a child process with BIGCODEC_DEBUG=1:
+audiotokenization_amd/_debug/libbigcodec_hip.so (build_lib.build(debug=True), built by __graft_entry__.build() next
+to the product library) is loaded by a child process with BIGCODEC_DEBUG=1:
   * bc_debug_selftest(n) makes n lanes fail a check on purpose: bc_debug_status reports exactly n failures and the
     check's line, and clears them;
   * the encode -> VQ -> decode of a small batch in h3 and x6, plus the conv / ResidualUnit / ResLSTM shapes of the
     encoder, run with every computed global access checked: 0 failures, and the outputs equal the product build's.
-Skipped when the debug library is absent or older than the sources (it is a developer tool, not the product).
+Fails when the debug library is absent or older than the sources.
 """
 import json
 import os
@@ -49,11 +49,11 @@ def test_debug_build_checks_and_selftest(tmp_path):
     from audiotokenization_amd import build_lib
 
     dlib = os.path.join(build_lib.DEBUG_DIR, "libbigcodec_hip.so")
-    if not os.path.exists(dlib):
-        pytest.skip("debug library not built (python audiotokenization_amd/build_lib.py --debug)")
+    # __graft_entry__.build() builds it; a missing or stale one is an error, not a skip
+    assert os.path.exists(dlib), "debug library not built (python audiotokenization_amd/build_lib.py --debug)"
     # the digest compiled into the library itself (bc_build_digest), not a side file
-    if build_lib.lib_digest(dlib) != build_lib._digest(build_lib._paths(True)[2]):
-        pytest.skip("debug library older than the sources")
+    assert build_lib.lib_digest(dlib) == build_lib._digest(build_lib._paths(True)[2]), \
+        "debug library older than the sources"
     dump = str(tmp_path / "dbg_")
     code = CHILD.format(repo=REPO, tests=os.path.join(REPO, "tests"), dump=dump)
     env = dict(os.environ, BIGCODEC_DEBUG="1")
