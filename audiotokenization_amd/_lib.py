@@ -62,6 +62,7 @@ _SIGS = {
     "bc_fsq_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "bc_fsq_codes": (I, [P, I, P, P, P, P, I, I, I, I, P]),
     "bc_stream_window": (I, [P, L, L, P, P, P, P, P, I, I, I, I, P]),
+    "bc_zero_tail": (I, [P, P, P, I, I, L, L, P]),
     "bc_resample_sinc": (I, [P, P, P, I, L, L, L, I, I, I, I, P]),
     "bc_rvq_update": (I, [P, P, P, L, I, P]),
     "bc_btc_to_ctb": (I, [P, P, I, I, I, P]),
@@ -81,7 +82,7 @@ EXPORTED = tuple(_SIGS)
 # measurement-only entry points a library of an earlier ABI lacks (tools/lab* A/B runs load such builds through
 # BIGCODEC_LIB_DIR); the product's own library exports them all (test_abi)
 _OPTIONAL = ("bc_launch_timer_enable", "bc_launch_timer_read")
-ABI_VERSION = 17  # include/bigcodec.h BC_ABI_VERSION
+ABI_VERSION = 18  # include/bigcodec.h BC_ABI_VERSION
 
 _ERR = {1: "bad argument", 2: "HIP launch error", 3: "unsupported shape"}
 

@@ -26,7 +26,7 @@ from . import ops
 from .conv import WNConv1d, WNConvTranspose1d
 from .modules import Activation1d, SnakeBeta, _DeviceCache, _as_input, _cpu, _pkey
 
-__all__ = ["ResidualUnit", "EncoderBlock", "DecoderBlock", "LSTM", "ResLSTM"]
+__all__ = ["ResidualUnit", "EncoderBlock", "DecoderBlock", "LSTM", "ResLSTM", "Ragged"]
 
 Flow = Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]
 
@@ -40,30 +40,103 @@ def _conv_of(m):
     return m.conv if hasattr(m, "conv") and not hasattr(m, "weight_v") else m
 
 
+class Ragged:
+    """Per-layer lengths of a ragged batch: clips of different lengths zero-padded into one (B, C, Tmax) batch.
+
+    Every non-causal conv zero-pads at the clip's end, so the padded batch computes what each clip computes alone as
+    long as every producer's output is exactly zero from the clip's own per-layer length to the padded end
+    (DESIGN.md "Ragged batches"): snake(0) = 0 keeps an activated tail zero, the ResidualUnit's inner k = 1 conv is
+    pointwise, the unidirectional LSTM never looks ahead and a transposed conv's first len * stride outputs read
+    inputs below len only.  The producers that must be masked are therefore: the input, the first conv, every
+    ResidualUnit, every strided and transposed conv, the ResLSTM (and the decoder's waveform).
+
+    `chain` lists those producers in flow order as (kind, module), kind in "conv", "convT", "unit", "keep"
+    (ragged_chain of the stacks); each row of the table is the lengths behind one of them, from the module's own
+    out_len on the host.  The table is uploaded once (one int32 H2D copy, no synchronisation per layer) and mask()
+    consumes the rows in order: one bc_zero_tail launch per producer (a dual raw + activated output shares it),
+    none when no clip of the batch is shorter than the padded row."""
+
+    def __init__(self, chain, lengths, T: int, what: str = "lengths"):
+        lens = np.asarray([int(v) for v in lengths], dtype=np.int64).reshape(-1)
+        if lens.size and int(lens.max()) > T:
+            raise ValueError(f"{what}: clip {int(lens.argmax())} has length {int(lens.max())} > {T}, the batch's")
+        self.rows, self.widths = [lens], [int(T)]
+        for kind, m in chain:
+            lens, T = self._step(kind, m, lens), int(self._step(kind, m, T))
+            if T <= 0 or (lens.size and int(lens.min()) <= 0):
+                b = int(lens.argmin()) if lens.size else 0
+                raise ValueError(f"{what}: clip {b} ({int(self.rows[0][b]) if lens.size else T}) is too short for "
+                                 f"this model (its B = 1 forward fails as well)")
+            self.rows.append(lens)
+            self.widths.append(T)
+        self.i = 0
+        self.table = None
+
+    def upload(self, device) -> "Ragged":
+        """The whole table to the device: the forward's one H2D copy."""
+        self.table = torch.from_numpy(np.stack(self.rows).astype(np.int32)).to(device)
+        return self
+
+    @staticmethod
+    def _step(kind, m, n):
+        if kind == "unit":
+            return _conv_of(m.block[3]).out_len(_conv_of(m.block[1]).out_len(n))
+        return n if kind == "keep" else _conv_of(m).out_len(n)
+
+    def mask(self, y, y2=None):
+        """Zero the tails of the next producer's output(s) in place; returns (y, y2)."""
+        i, self.i = self.i, self.i + 1
+        t = y if y is not None else y2
+        if i >= len(self.rows) or t.shape[-1] != self.widths[i] or t.shape[0] != self.rows[i].size:
+            raise RuntimeError(f"ragged flow out of step with its length table at producer {i}: output "
+                               f"{tuple(t.shape)}, expected width {self.widths[i] if i < len(self.widths) else None}")
+        tail_max = self.widths[i] - int(self.rows[i].min())
+        if tail_max > 0:
+            a, b = (y, y2) if y is not None else (y2, None)
+            ops.load().zero_tail_(a, b, self.table[i], tail_max)
+        return y, y2
+
+    def masked_input(self, x):
+        """The batch with zeros past each clip's length, in a copy: the caller's tensor keeps its tail."""
+        if self.widths[0] - int(self.rows[0].min()) > 0:
+            x = x.clone()
+        return self.mask(x)[0]
+
+
+def _masked(rg: Optional[Ragged], out):
+    """Zero the ragged tails of a producer's output: a tensor, or a (raw, activated) Flow pair."""
+    if rg is None:
+        return out
+    if isinstance(out, tuple):
+        return rg.mask(*out)
+    return rg.mask(out)[0]
+
+
 def produce_conv(conv, inp, residual=None, want_raw=True, next_act: Optional[Activation1d] = None,
-                 epilogue: int = 0) -> Flow:
+                 epilogue: int = 0, rg: Optional[Ragged] = None) -> Flow:
     """Run `conv` on an already-activated input and hand its output to `next_act`'s consumer."""
     if next_act is None:
-        return conv.run(inp, residual, epilogue), None
+        return _masked(rg, conv.run(inp, residual, epilogue)), None
     if _fusable(next_act):
         co = next_act.act.coeffs(inp.device)
         if want_raw:
             y, ya = conv.run(inp, residual, epilogue, out_snake=co, dual=True)
-            return y, ya
-        return None, conv.run(inp, residual, epilogue, out_snake=co)
-    y = conv.run(inp, residual, epilogue)
+            return _masked(rg, (y, ya))
+        return None, _masked(rg, conv.run(inp, residual, epilogue, out_snake=co))
+    y = _masked(rg, conv.run(inp, residual, epilogue))
     return y, next_act(y)
 
 
-def produce_convT(conv, inp, want_raw=True, next_act: Optional[Activation1d] = None) -> Flow:
+def produce_convT(conv, inp, want_raw=True, next_act: Optional[Activation1d] = None,
+                  rg: Optional[Ragged] = None) -> Flow:
     if next_act is None:
-        return conv.run(inp), None
+        return _masked(rg, conv.run(inp)), None
     if _fusable(next_act):
         co = next_act.act.coeffs(inp.device)
         if want_raw:
-            return conv.run(inp, out_snake=co, dual=True)
-        return None, conv.run(inp, out_snake=co)
-    y = conv.run(inp)
+            return _masked(rg, conv.run(inp, out_snake=co, dual=True))
+        return None, _masked(rg, conv.run(inp, out_snake=co))
+    y = _masked(rg, conv.run(inp))
     return y, next_act(y)
 
 
@@ -101,16 +174,17 @@ class ResidualUnit(nn.Module):
             return False
         return self._fused_cfg() >= 0
 
-    def flow(self, x_raw, x_act, want_raw=True, next_act=None) -> Flow:
-        """x_act = self.first_act(x_raw) computed by the producer, or None (snake_on_load)."""
+    def flow(self, x_raw, x_act, want_raw=True, next_act=None, rg: Optional[Ragged] = None) -> Flow:
+        """x_act = self.first_act(x_raw) computed by the producer, or None (snake_on_load).  rg: the unit's OUTPUT
+        gets the ragged batch's zero tails (the inner k = 1 conv is pointwise: the k = 7 conv's output needs none)."""
         if next_act is None or _fusable(next_act):
             cfg = self._fused_cfg()
             if cfg >= 0:
-                return self._flow_fused(cfg, x_raw, x_act, want_raw, next_act)
+                return _masked(rg, self._flow_fused(cfg, x_raw, x_act, want_raw, next_act))
         if x_act is None:
             x_act = self.first_act(x_raw)
         _, h = produce_conv(self.block[1], x_act, None, want_raw=False, next_act=self.block[2])
-        return produce_conv(self.block[3], h, residual=x_raw, want_raw=want_raw, next_act=next_act)
+        return produce_conv(self.block[3], h, residual=x_raw, want_raw=want_raw, next_act=next_act, rg=rg)
 
     def _flow_fused(self, cfg, x_raw, x_act, want_raw, next_act) -> Flow:
         conv7, conv1 = _conv_of(self.block[1]), _conv_of(self.block[3])
@@ -175,14 +249,19 @@ class EncoderBlock(nn.Module):
     def first_act(self) -> Activation1d:
         return self.block[0].first_act
 
-    def flow(self, x_raw, x_act, want_raw=True, next_act=None) -> Flow:
+    def ragged_chain(self):
+        """The block's masked producers in flow order (Ragged)."""
+        n = len(self.block)
+        return [("unit", self.block[i]) for i in range(n - 2)] + [("conv", self.block[n - 1])]
+
+    def flow(self, x_raw, x_act, want_raw=True, next_act=None, rg: Optional[Ragged] = None) -> Flow:
         n = len(self.block)
         rus = [self.block[i] for i in range(n - 2)]
         for i, ru in enumerate(rus):
             last = i == len(rus) - 1
             nxt = self.block[n - 2] if last else input_act(rus[i + 1])
-            x_raw, x_act = ru.flow(x_raw, x_act, want_raw=not last, next_act=nxt)
-        return produce_conv(self.block[n - 1], x_act, None, want_raw=want_raw, next_act=next_act)
+            x_raw, x_act = ru.flow(x_raw, x_act, want_raw=not last, next_act=nxt, rg=rg)
+        return produce_conv(self.block[n - 1], x_act, None, want_raw=want_raw, next_act=next_act, rg=rg)
 
     def forward(self, x):
         x = _as_input(x)
@@ -212,14 +291,18 @@ class DecoderBlock(nn.Module):
     def first_act(self) -> Activation1d:
         return self.block[0]
 
-    def flow(self, x_raw, x_act, want_raw=True, next_act=None) -> Flow:
+    def ragged_chain(self):
+        """The block's masked producers in flow order (Ragged)."""
+        return [("convT", self.block[1])] + [("unit", self.block[i]) for i in range(2, len(self.block))]
+
+    def flow(self, x_raw, x_act, want_raw=True, next_act=None, rg: Optional[Ragged] = None) -> Flow:
         rus = [self.block[i] for i in range(2, len(self.block))]
         y_raw, y_act = produce_convT(self.block[1], x_act, want_raw=True,
-                                     next_act=input_act(rus[0]) if rus else next_act)
+                                     next_act=input_act(rus[0]) if rus else next_act, rg=rg)
         for i, ru in enumerate(rus):
             last = i == len(rus) - 1
             y_raw, y_act = ru.flow(y_raw, y_act, want_raw=(want_raw if last else True),
-                                   next_act=next_act if last else input_act(rus[i + 1]))
+                                   next_act=next_act if last else input_act(rus[i + 1]), rg=rg)
         return y_raw, y_act
 
     def forward(self, x):
@@ -323,12 +406,17 @@ class ResLSTM(nn.Module):
             return out[0], (out[2], out[3])
         return out[0]
 
-    def flow(self, x_raw, want_raw=True, next_act=None) -> Flow:
+    def flow(self, x_raw, want_raw=True, next_act=None, rg: Optional[Ragged] = None) -> Flow:
+        """rg: a ragged batch.  The forward recurrence never looks ahead, so a clip's own steps are the per-clip ones;
+        the steps past its end (the LSTM running on over zeros) get the zero tail."""
+        if rg is not None and self.lstm.bidirectional:
+            raise NotImplementedError("a ragged batch needs a unidirectional ResLSTM: the reverse direction would "
+                                      "have to start at each clip's own end")
         if next_act is None:
-            return self.run(x_raw), None
+            return _masked(rg, self.run(x_raw)), None
         if _fusable(next_act) and not want_raw:
-            return None, self.run(x_raw, out_snake=next_act.act.coeffs(x_raw.device))
-        y = self.run(x_raw)
+            return None, _masked(rg, self.run(x_raw, out_snake=next_act.act.coeffs(x_raw.device)))
+        y = _masked(rg, self.run(x_raw))
         return y, next_act(y)
 
     def forward(self, x):

@@ -634,6 +634,14 @@ int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_s
                               n, P, S(stream));
 }
 
+int bc_zero_tail(float* y, float* y2, const int* lens, int B, int C, long long T, long long tail_max, void* stream) {
+  if (!y || !lens || B <= 0 || C <= 0 || T <= 0) return BC_ERR_ARG;
+  if (tail_max <= 0) return BC_OK;
+  const double cells = (double)B * C * (double)(tail_max < T ? tail_max : T);  // an upper bound: the shortest clip's tail
+  LTScope lt("zero_tail_kernel", 0.0, 4.0 * cells * (y2 ? 2 : 1), S(stream));
+  return zero_tail_launch(y, y2, lens, B, C, T, tail_max, S(stream));
+}
+
 int bc_fsq_codes(const void* idx, int idx_bits, const int* levels, const float* w_out, const float* b_out,
                  float* post, int B, int D, int T, int d, void* stream) {
   return fsq_codes_launch(idx, idx_bits, levels, w_out, b_out, post, B, D, T, d, S(stream));
@@ -717,6 +725,7 @@ int bc_dbg_fetch_resunit_w16(unsigned*);
 int bc_dbg_fetch_resunit_rr(unsigned*);
 int bc_dbg_fetch_pw_presplit(unsigned*);
 int bc_dbg_fetch_lstm_seq(unsigned*);
+int bc_dbg_fetch_elementwise(unsigned*);
 int bc_debug_status(unsigned* out) {
   if (!out) return BC_ERR_ARG;
   if (hipDeviceSynchronize() != hipSuccess) return BC_ERR_LAUNCH;
@@ -724,7 +733,8 @@ int bc_debug_status(unsigned* out) {
   int (*const fetch[])(unsigned*) = {bc_dbg_fetch_conv1d, bc_dbg_fetch_conv1d_x6_p1, bc_dbg_fetch_conv1d_x6_p2, bc_dbg_fetch_conv1d_x6ra,
                                      bc_dbg_fetch_conv1d_x6_p3, bc_dbg_fetch_resunit_x6, bc_dbg_fetch_resunit_w16,
                                      bc_dbg_fetch_resunit_rr,
-                                     bc_dbg_fetch_pw_presplit, bc_dbg_fetch_lstm_seq, bc_dbg_fetch_abi};
+                                     bc_dbg_fetch_pw_presplit, bc_dbg_fetch_lstm_seq, bc_dbg_fetch_elementwise,
+                                     bc_dbg_fetch_abi};
   for (auto f : fetch)
     if (f(out)) return BC_ERR_LAUNCH;
   return BC_OK;

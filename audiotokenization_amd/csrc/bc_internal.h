@@ -92,6 +92,7 @@ int snake_launch(const float* x, const float* sa, const float* sb, float* y, int
                  long long T, hipStream_t st);
 int stream_window_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa, const float* sb,
                          float* win, float* ctx_out, int B, int C, int n, int P, hipStream_t st);
+int zero_tail_launch(float* y, float* y2, const int* lens, int B, int C, long long T, long long tail_max, hipStream_t st);
 int aa_snake_launch(const float* x, const float* sa, const float* sb, const float* fu,
                     const float* fd, float* y, int B, int C, int T, hipStream_t st);
 int btc_to_ctb_launch(const float* x, float* y, int B, int C, int T, hipStream_t st);

@@ -11,6 +11,7 @@
 //  transpose kernels: [B][C][T] <-> [C][T][B] layouts around the ResLSTM (vq/module.py:160-166).
 //  synth_clips      : counter-hash white noise generated in HBM.
 //  stream_window    : a causal stream's [carried context | chunk] window (+ Snake) and its next context.
+//  zero_tail        : zeros from each clip's own length to the padded end of a ragged batch's rows.
 #include <algorithm>
 #include "bc_common.h"
 #include "bc_internal.h"
@@ -235,6 +236,57 @@ int stream_window_launch(const float* x, long long xbs, long long xT, const floa
   return BC_OK;
 }
 
+// Ragged batches (blocks.py Ragged): clips of different lengths share one zero-padded batch, and the computation stays
+// the per-clip one as long as every producer's output is exactly zero from the clip's own per-layer length lens[b] to
+// the padded end T (the zero padding every conv of the per-clip forward reads there).  For each row (b, c) of y (and of
+// y2, the activated twin of a dual output) this stores 0.0f at t in [clamp(lens[b], 0, T), T): stores, never a
+// multiplication by a mask, since the tail may hold Inf / NaN.  Only the tails are touched: grid x walks groups of four
+// floats from the 16-byte boundary at or below the row's first tail element (16-byte stores for whole groups when
+// vec: y and y2 16-byte aligned; single floats for the unaligned head, the end of the row and unaligned views), grid
+// y the rows (one 32-bit division per row), so the cost scales with the padding, tail_max = T - min(lens) columns at
+// the most, and a row with lens[b] >= T does nothing.  total = rows * T bounds the debug build's index guards.
+__global__ void __launch_bounds__(256) zero_tail_kernel(float* __restrict__ y, float* __restrict__ y2,
+                                                        const int* __restrict__ lens, int C, long long T, int rows,
+                                                        long long total, bool vec) {
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = row / C;
+    long long len = lens[b];
+    len = len < 0 ? 0 : len;
+    if (len >= T) continue;
+    const long long first = (long long)row * T + len, end = (long long)row * T + T;  // the tail's elements of y
+    const long long g0 = first & ~3LL;
+    for (long long e = g0 + 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x); e < end;
+         e += 4LL * gridDim.x * blockDim.x) {
+      if (vec && e >= first && e + 4 <= end) {
+        if (!BC_DOK(e >= 0 && e + 3 < total)) continue;
+        *reinterpret_cast<floatx4*>(y + e) = floatx4{0.f, 0.f, 0.f, 0.f};
+        if (y2) *reinterpret_cast<floatx4*>(y2 + e) = floatx4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        const long long lo = e < first ? first : e, hi = e + 4 < end ? e + 4 : end;
+        for (long long i = lo; i < hi; ++i) {
+          if (!BC_DOK(i >= 0 && i < total)) break;
+          y[i] = 0.f;
+          if (y2) y2[i] = 0.f;
+        }
+      }
+    }
+  }
+}
+
+int zero_tail_launch(float* y, float* y2, const int* lens, int B, int C, long long T, long long tail_max, hipStream_t st) {
+  if (!y || !lens || B <= 0 || C <= 0 || T <= 0) return BC_ERR_ARG;
+  if (tail_max <= 0) return BC_OK;  // every clip fills the batch: nothing to zero
+  const long long rows = (long long)B * C;
+  if (rows > 0x7fffffffLL || T > (1LL << 62) / rows) return BC_ERR_UNSUPPORTED;
+  if (tail_max > T) tail_max = T;
+  const long long groups = (tail_max + 3) / 4 + 1;  // (+1: the group that straddles the tail's first element)
+  const int gx = (int)std::min<long long>((groups + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
+  const bool vec = (((unsigned long long)y | (unsigned long long)y2) & 15) == 0;
+  hipLaunchKernelGGL(zero_tail_kernel, dim3(gx, gy), dim3(256), 0, st, y, y2, lens, C, T, (int)rows, rows * T, vec);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
 // Activation1d with any (up_ratio, up taps, down_ratio, down taps) (act.py:8-23 constructor arguments):
 // the same three stages as aa_snake_kernel, with the geometry of resample.py:10-33 / filter.py:86-95 at
 // run time.  Up: replicate pad P = Ku / ru - 1, transposed conv stride ru, x ru, crop [PL, -PR) with
@@ -452,3 +504,5 @@ int convT_interleave_launch(const float* ph, const float* ph2, float* y, float* 
 }
 
 }  // namespace bc
+
+BC_DEBUG_EXPORT(elementwise)

@@ -403,6 +403,26 @@ std::vector<Tensor> stream_window(const Tensor& x, const optional<Tensor>& ctx, 
   return {win, nctx};
 }
 
+// ---- zero_tail_: the zero tails of a ragged batch (each clip's own length to the padded end) -------------------
+void zero_tail_(const Tensor& y, const optional<Tensor>& y2, const Tensor& lens, int64_t tail_max) {
+  dev(y, "y");
+  TORCH_CHECK_VALUE(y.dim() == 3, "bigcodec::zero_tail_: y must be (B, C, T)");
+  dev(lens, "lens", at::kInt);
+  same_device(y, lens, "lens");
+  TORCH_CHECK_VALUE(lens.dim() == 1 && lens.size(0) == y.size(0), "bigcodec::zero_tail_: lens must be (B,) int32");
+  float* p2 = nullptr;
+  if (y2.has_value()) {
+    dev(*y2, "y2");
+    same_device(y, *y2, "y2");
+    TORCH_CHECK_VALUE(y2->sizes() == y.sizes(), "bigcodec::zero_tail_: y2 ", y2->sizes(), " != y ", y.sizes());
+    p2 = y2->data_ptr<float>();
+  }
+  if (y.numel() == 0) return;
+  ok(bc_zero_tail(y.data_ptr<float>(), p2, lens.data_ptr<int>(), i32(y.size(0), "B"), i32(y.size(1), "C"), y.size(2),
+                  tail_max, stream_of(y)),
+     "bc_zero_tail");
+}
+
 Tensor fsq_codes(const Tensor& idx, const Tensor& w_out, const Tensor& b_out, at::IntArrayRef levels) {
   TORCH_CHECK_VALUE(idx.is_cuda() && (idx.scalar_type() == at::kInt || idx.scalar_type() == at::kLong) &&
                         idx.is_contiguous(),
@@ -501,6 +521,7 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("fsq(Tensor z, Tensor w_in, Tensor b_in, Tensor w_out, Tensor b_out, Tensor consts) -> Tensor[]");
   m.def("fsq_codes(Tensor idx, Tensor w_out, Tensor b_out, int[] levels) -> Tensor");
   m.def("stream_window(Tensor x, Tensor? ctx, Tensor? alpha_exp, Tensor? inv_beta, int P) -> Tensor[]");
+  m.def("zero_tail_(Tensor(a!) y, Tensor(b!)? y2, Tensor lens, int tail_max) -> ()");
   m.def("resample_sinc(Tensor x, Tensor kern, int lout, int pitch, int orig, int new_freq, int taps, int width) -> Tensor");
   m.def("synth_clips_(Tensor(a!) x, int clip0) -> ()");
 }
@@ -525,6 +546,7 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("fsq", &Guarded<&fsq>::call);
   m.impl("fsq_codes", &Guarded<&fsq_codes>::call);
   m.impl("stream_window", &Guarded<&stream_window>::call);
+  m.impl("zero_tail_", &Guarded<&zero_tail_>::call);
   m.impl("resample_sinc", &Guarded<&resample_sinc>::call);
   m.impl("synth_clips_", &Guarded<&synth_clips_>::call);
 }

@@ -74,13 +74,22 @@ class BigCodecModel(torch.nn.Module):
         self.codebook_size = lm.cfg.model.codec_decoder.codebook_size
 
     @torch.no_grad()
-    def forward(self, x):
-        vq_emb = self.lm.model["CodecEnc"](x)
-        vq_post_emb, vq_code, _ = self.lm.model["generator"](vq_emb, vq=True)
-        if not self.reconstruct:
-            return {"indices": vq_code}
-        recon = self.lm.model["generator"](vq_post_emb, vq=False)
-        return {"x_rec": recon, "indices": vq_code, "loss": {}}
+    def forward(self, x, lengths=None):
+        """lengths (samples per clip): a ragged batch (BigCodecEncoder.forward); the dict then carries "frames", each
+        clip's valid extent of "indices" (Nq, B, Fmax) (and, times the hop, of "x_rec")."""
+        enc, gen = self.lm.model["CodecEnc"], self.lm.model["generator"]
+        if lengths is None:
+            vq_emb, frames = enc(x), None
+        else:
+            vq_emb, frames = enc(x, lengths=lengths), enc.frame_lengths(lengths)
+        vq_post_emb, vq_code, _ = gen(vq_emb, vq=True)
+        out = {"indices": vq_code}
+        if self.reconstruct:
+            recon = gen(vq_post_emb, vq=False) if frames is None else gen(vq_post_emb, vq=False, lengths=frames)
+            out = {"x_rec": recon, "indices": vq_code, "loss": {}}
+        if frames is not None:
+            out["frames"] = frames
+        return out
 
 
 def pad_like_inference_full(x: torch.Tensor, hop: int = 200) -> torch.Tensor:
@@ -479,16 +488,121 @@ def build_lm(save_path: str, device):
     return CodecLightningModule.from_checkpoint(ckpt_path, load_config(config_path)).to(device).eval()
 
 
+READ_AHEAD = 8  # run_extraction(batch > 1): the window of decoded files that is sorted by length, in batches
+
+
+def plan_batches(lengths, batch: int, window: Optional[int] = None) -> List[List[int]]:
+    """Group items [0, len(lengths)) into ragged batches of at most `batch`: the list is cut into consecutive windows
+    of `window` items (default READ_AHEAD * batch: what the extraction loop holds decoded at a time), each window is
+    sorted by length (ties by position) and cut into consecutive groups, so the members of a group are the window's
+    closest in length and little of a batch is padding.  A pure function of its arguments; every item appears in
+    exactly one group."""
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
+    window = READ_AHEAD * batch if window is None else window
+    if window < 1:
+        raise ValueError("window must be >= 1")
+    groups = []
+    for lo in range(0, len(lengths), window):
+        order = sorted(range(lo, min(lo + window, len(lengths))), key=lambda i: (lengths[i], i))
+        groups += [order[k:k + batch] for k in range(0, len(order), batch)]
+    return groups
+
+
+def _run_extraction_batched(model, mine, output_dir, sample_rate, duration, device, workers, batch, read, log):
+    """run_extraction with batch > 1: a window of READ_AHEAD * batch files is decoded (host threads, reading ahead
+    into the next window) and resampled, sorted by length (plan_batches) and encoded in ragged batches
+    (BigCodecModel.forward(x, lengths)): each clip's codes are the ones its own B = 1 encode gives.  A file that fails
+    to decode is counted alone; when a batch's encode raises, its members are encoded one by one, so one bad file
+    costs one file and the files written and the counts do not depend on the batching."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from .ingest import load_item
+
+    saved = errors = 0
+    window = READ_AHEAD * batch
+    ahead = window + max(1, workers)
+
+    def encode_one(wav):
+        with torch.no_grad():
+            out = model(wav.unsqueeze(0))
+        indices = out.get("indices") if isinstance(out, dict) else None
+        return None if indices is None else indices_to_numpy(indices)
+
+    def encode_group(wavs):
+        if len(wavs) == 1:
+            return [encode_one(wavs[0])]
+        lens = [int(w.shape[1]) for w in wavs]
+        x = torch.zeros((len(wavs), 1, max(lens)), device=wavs[0].device, dtype=torch.float32)
+        for b, w in enumerate(wavs):
+            x[b, :, :lens[b]] = w  # (a clip with another channel count fails here: the group is retried one by one)
+        with torch.no_grad():
+            out = model(x, lengths=lens)
+        codes, frames = out["indices"], out["frames"]
+        return [indices_to_numpy(codes[:, b:b + 1, :frames[b]]) for b in range(len(wavs))]
+
+    def save(subset, fileid, arr):
+        nonlocal saved, errors
+        try:
+            if arr is None:
+                log(f"Warning: No indices found for file: {fileid}. Skipping.")
+                errors += 1
+                return
+            save_indices(output_dir, subset, fileid, arr)
+            saved += 1
+        except Exception as e:
+            log(f"Error processing {fileid}: {type(e).__name__}: {e}")
+            errors += 1
+
+    with ThreadPoolExecutor(max_workers=max(1, workers)) as pool:
+        futs = {j: pool.submit(read, mine[j]) for j in range(min(ahead, len(mine)))}
+        for w0 in range(0, len(mine), window):
+            ready = []  # (subset, fileid, wav (C, T) on the device)
+            for i in range(w0, min(w0 + window, len(mine))):
+                if i + ahead < len(mine):
+                    futs[i + ahead] = pool.submit(read, mine[i + ahead])
+                subset, _, fileid = mine[i]
+                try:
+                    x, sr = futs.pop(i).result()
+                    wav, _ = load_item(None, sample_rate, duration, None, device, decoded=(x, sr))
+                    ready.append((subset, fileid, wav))
+                except Exception as e:  # extract_indices.py:565-574: counted, not fatal
+                    log(f"Error processing {fileid}: {type(e).__name__}: {e}")
+                    errors += 1
+            for group in plan_batches([int(r[2].shape[1]) for r in ready], batch, window=max(1, len(ready))):
+                members = [ready[j] for j in group]
+                try:
+                    arrs = encode_group([m[2] for m in members])
+                except Exception:
+                    arrs = None
+                for k, (subset, fileid, wav) in enumerate(members):
+                    if arrs is not None:
+                        save(subset, fileid, arrs[k])
+                        continue
+                    try:  # the batch failed: every member alone, as the per-file loop would
+                        arr = encode_one(wav)
+                    except Exception as e:
+                        log(f"Error processing {fileid}: {type(e).__name__}: {e}")
+                        errors += 1
+                        continue
+                    save(subset, fileid, arr)
+    return saved, errors
+
+
 def run_extraction(lm, items, output_dir: str, sample_rate: Optional[int], duration: Optional[float],
-                   ext_audio: str, device, rank: int = 0, world: int = 1, workers: int = 4, log=print):
+                   ext_audio: str, device, rank: int = 0, world: int = 1, workers: int = 4, log=print, batch: int = 1):
     """The extraction loop (extract_indices.py:497-574) for this rank's block of the file list: host decode
     (FLAC / WAV) of the next files on `workers` threads while the current one runs on the GPU, then
     resample (GPU) -> encode -> VQ -> (F, Nq) int16 -> <output_dir>/<subset>/<spk>/<chapter>/<fileid>.npy.
-    Per-file failures are counted, not fatal.  Returns (saved, errors) of this rank."""
+    Per-file failures are counted, not fatal.  Returns (saved, errors) of this rank.  batch = 1 (the default)
+    encodes every file alone, as the reference does; batch > 1 encodes ragged batches of files of similar length
+    (_run_extraction_batched), with the same files written and the same counts."""
     from concurrent.futures import ThreadPoolExecutor
 
     from .ingest import read_audio, load_item
 
+    if batch < 1:
+        raise ValueError("batch must be >= 1")
     model = BigCodecModel(lm)
     lo, hi = shard_range(len(items), rank, world)
     mine = items[lo:hi]
@@ -502,6 +616,9 @@ def run_extraction(lm, items, output_dir: str, sample_rate: Optional[int], durat
         return read_audio(path)
 
     workers = max(1, workers)
+    if batch > 1:
+        return _run_extraction_batched(model, mine, output_dir, sample_rate, duration, device, workers, batch, read,
+                                       log)
     with ThreadPoolExecutor(max_workers=workers) as pool:
         futs = {j: pool.submit(read, mine[j]) for j in range(min(workers, len(mine)))}
         for i, (subset, _, fileid) in enumerate(mine):
@@ -527,7 +644,7 @@ def run_extraction(lm, items, output_dir: str, sample_rate: Optional[int], durat
 
 def main(argv=None):
     """python -m audiotokenization_amd.extract --save_path RUN --subsets test-clean [...] — the reference
-    CLI's arguments (extract_indices.py:379-389); --workers (host decode threads) is this build's own.
+    CLI's arguments (extract_indices.py:379-389); --workers (host decode threads) and --batch (files per ragged encode, default 1) are this build's own.
     Under torchrun every rank extracts its block of the file list (clip-sharded, no collective on the
     data path; the saved / error counts are summed at the end)."""
     import argparse
@@ -543,7 +660,13 @@ def main(argv=None):
     p.add_argument("--ext_audio", type=str, default=".flac")
     p.add_argument("--subsets", type=str, nargs="+", required=True)
     p.add_argument("--workers", type=int, default=4)
+    p.add_argument("--batch", type=int, default=1,
+                   help="files per encode: 1 = every file alone (the reference's loop); N > 1 = ragged batches of N "
+                        "files of similar length, same index files")
     a = p.parse_args(argv)
+    if a.batch < 1:
+        print(f"Error: --batch must be >= 1 (got {a.batch})")
+        return 1
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -566,7 +689,7 @@ def main(argv=None):
     if rank == 0:
         print(f"Dataset size: {len(items)} files, {world} rank(s)")
     saved, errors = run_extraction(lm, items, output_dir, a.sample_rate, a.duration, a.ext_audio, device, rank,
-                                   world, a.workers)
+                                   world, a.workers, batch=a.batch)
     if world > 1:
         t = torch.tensor([saved, errors], device=device, dtype=torch.int64)
         dist.all_reduce(t)

@@ -25,7 +25,8 @@ _ns = None
 
 # every op the extension defines (tests check the registry against this list)
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
-       "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_")
+       "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
+       "zero_tail_")
 
 
 def load():
@@ -153,6 +154,10 @@ def _register_fakes():
     @reg("bigcodec::resample_sinc")
     def _resample(x, kern, lout, pitch, orig, new_freq, taps, width):
         return _new(x, tuple(x.shape[:-1]) + (pitch,))
+
+    @reg("bigcodec::zero_tail_")
+    def _zero_tail(y, y2, lens, tail_max):
+        return None
 
     @reg("bigcodec::synth_clips_")
     def _synth(x, clip0):

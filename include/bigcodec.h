@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define BC_ABI_VERSION 17
+#define BC_ABI_VERSION 18
 
 int bc_abi_version(void);
 /* bc_build_digest: sha256 (64 hex characters) of the sources, headers and compiler flags this library was built
@@ -279,6 +279,15 @@ int bc_fsq_codes(const void* idx, int idx_bits, const int* levels, const float* 
 int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_stride, const float* ctx,
                      const float* snake_alpha_exp, const float* snake_inv_beta, float* win, float* ctx_out, int B, int C,
                      int n, int P, void* stream);
+
+/* bc_zero_tail (ABI 18): ragged batches (clips of different lengths zero-padded into one batch; the reference encodes
+ *   each file alone, extract_indices.py:497-561, and its convs zero-pad at the clip's end, vq/module.py:45-48, 59-72).
+ *   For y[B][C][T], the optional y2 of the same shape (NULL: none) and the DEVICE array lens[B], stores 0.0f at every
+ *   t in [clamp(lens[b], 0, T), T) of every row (b, c): stores, not a product with a mask, so Inf / NaN in a tail
+ *   become zero.  tail_max = T - min(lens) is computed by the host and only sizes the launch to the padding (a larger
+ *   value costs idle threads, a smaller one nothing but time); tail_max <= 0 launches nothing.  Returns 1 for a null
+ *   y or lens or a non-positive B, C or T. */
+int bc_zero_tail(float* y, float* y2, const int* lens, int B, int C, long long T, long long tail_max, void* stream);
 
 /* ---- Real-audio ingest ------------------------------------------------------------------------
  * bc_resample_sinc: torchaudio.transforms.Resample(orig, new) as extract_indices.py:129-132 and
