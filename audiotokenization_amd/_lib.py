@@ -69,6 +69,11 @@ _SIGS = {
     "bc_ctb_to_btc_add": (I, [P, P, P, I, I, I, P]),
     "bc_synth_clips": (I, [P, I, L, L, P]),
     "bc_tanh_fwd": (I, [P, P, L, P]),
+    "bc_si_snr": (I, [P, P, P, P, I, L, P]),
+    "bc_logmel_tile_frames": (I, []),
+    "bc_logmel_workspace_doubles": (L, [I, L, I]),
+    "bc_logmel_l1": (I, [P, P, P, P, P, P, P, I, L, I, I, C.c_float, P]),
+    "bc_code_hist": (I, [P, I, P, P, I, L, I, P]),
     "bc_flac_info": (I, [P, L, P, P, P, P]),
     "bc_flac_decode": (L, [P, L, P, I, L, I]),
     "bc_conv1d_kernel_name": (I, [I, I, I, I, C.c_char_p, I]),

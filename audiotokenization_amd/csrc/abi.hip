@@ -695,6 +695,33 @@ int bc_synth_clips(float* x, int B, long long T, long long clip0, void* stream) 
   return synth_clips_launch(x, B, T, clip0, S(stream));
 }
 
+int bc_si_snr(const float* ref, const float* rec, const int* lens, float* out, int B, long long T, void* stream) {
+  if (!ref || !rec || !out || B <= 0 || T <= 0) return BC_ERR_ARG;
+  LTScope lt("si_snr_kernel", 14.0 * B * (double)T, 24.0 * B * (double)T, S(stream));
+  return si_snr_launch(ref, rec, lens, out, B, T, S(stream));
+}
+
+int bc_logmel_tile_frames(void) { return logmel_tile_frames(); }
+
+long long bc_logmel_workspace_doubles(int B, long long T, int n_fft) { return logmel_workspace_doubles(B, T, n_fft); }
+
+int bc_logmel_l1(const float* ref, const float* rec, const int* lens, const float* basis, const float* mel, float* out,
+                 double* workspace, int B, long long T, int n_fft, int n_mels, float clamp_eps, void* stream) {
+  if (!ref || !rec || !basis || !mel || !out || !workspace || B <= 0 || T <= 0 || n_fft <= 0 || n_mels <= 0)
+    return BC_ERR_ARG;
+  // both signals: (re, im) basis x frames, then mel x magnitudes, over the padded batch's frames
+  const double cols = 2.0 * B * (1.0 + (double)(T / (n_fft / 4 > 0 ? n_fft / 4 : 1))), bins = n_fft / 2 + 1;
+  LTScope lt("logmel_l1_kernel", cols * 2.0 * bins * (2.0 * n_fft + n_mels), 8.0 * B * (double)T, S(stream));
+  return logmel_l1_launch(ref, rec, lens, basis, mel, out, workspace, B, T, n_fft, n_mels, clamp_eps, S(stream));
+}
+
+int bc_code_hist(const void* codes, int code_bits, const int* lens, long long* counts, int B, long long T, int n_codes,
+                 void* stream) {
+  if (!codes || !counts || B <= 0 || T <= 0 || n_codes <= 0) return BC_ERR_ARG;
+  LTScope lt("code_hist_kernel", 0.0, (code_bits / 8.0) * B * (double)T, S(stream));
+  return code_hist_launch(codes, code_bits, lens, counts, B, T, n_codes, S(stream));
+}
+
 }  // extern "C"
 
 // Diagnostics only (not part of include/bigcodec.h): run the unidirectional ResLSTM's input projection on the
@@ -726,6 +753,7 @@ int bc_dbg_fetch_resunit_rr(unsigned*);
 int bc_dbg_fetch_pw_presplit(unsigned*);
 int bc_dbg_fetch_lstm_seq(unsigned*);
 int bc_dbg_fetch_elementwise(unsigned*);
+int bc_dbg_fetch_metrics(unsigned*);
 int bc_debug_status(unsigned* out) {
   if (!out) return BC_ERR_ARG;
   if (hipDeviceSynchronize() != hipSuccess) return BC_ERR_LAUNCH;
@@ -733,7 +761,7 @@ int bc_debug_status(unsigned* out) {
   int (*const fetch[])(unsigned*) = {bc_dbg_fetch_conv1d, bc_dbg_fetch_conv1d_x6_p1, bc_dbg_fetch_conv1d_x6_p2, bc_dbg_fetch_conv1d_x6ra,
                                      bc_dbg_fetch_conv1d_x6_p3, bc_dbg_fetch_resunit_x6, bc_dbg_fetch_resunit_w16,
                                      bc_dbg_fetch_resunit_rr,
-                                     bc_dbg_fetch_pw_presplit, bc_dbg_fetch_lstm_seq, bc_dbg_fetch_elementwise,
+                                     bc_dbg_fetch_pw_presplit, bc_dbg_fetch_lstm_seq, bc_dbg_fetch_elementwise, bc_dbg_fetch_metrics,
                                      bc_dbg_fetch_abi};
   for (auto f : fetch)
     if (f(out)) return BC_ERR_LAUNCH;

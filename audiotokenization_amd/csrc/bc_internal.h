@@ -154,4 +154,14 @@ int vq2emb_launch(const long long* idx, long long idx_stride, const float* cb, c
                   hipStream_t st);
 int rvq_update_launch(float* residual, float* out, const float* q, long long n, int first,
                       hipStream_t st);
+
+// round-trip quality metrics (metrics.hip)
+int si_snr_launch(const float* ref, const float* rec, const int* lens, float* out, int B, long long T, hipStream_t st);
+int logmel_tile_frames();
+long long logmel_workspace_doubles(int B, long long T, int n_fft);
+int logmel_l1_launch(const float* ref, const float* rec, const int* lens, const float* basis, const float* melw,
+                     float* out, double* ws, int B, long long T, int n_fft, int n_mels, float clamp_eps,
+                     hipStream_t st);
+int code_hist_launch(const void* codes, int code_bits, const int* lens, long long* counts, int B, long long T,
+                     int n_codes, hipStream_t st);
 }  // namespace bc

@@ -477,6 +477,73 @@ void synth_clips_(const Tensor& x, int64_t clip0) {
   ok(bc_synth_clips(x.data_ptr<float>(), i32(B, "B"), T, clip0, stream_of(x)), "bc_synth_clips");
 }
 
+// ---- round-trip quality metrics (csrc/metrics.hip) ----------------------------------------------------------------
+const int* opt_lens(const Tensor& ref, const optional<Tensor>& lens, int64_t B, const char* op) {
+  if (!lens.has_value()) return nullptr;
+  dev(*lens, "lens", at::kInt);
+  same_device(ref, *lens, "lens");
+  TORCH_CHECK_VALUE(lens->dim() == 1 && lens->size(0) == B, "bigcodec::", op, ": lens must be (B,) int32");
+  return lens->data_ptr<int>();
+}
+
+void check_pair(const Tensor& ref, const Tensor& rec, const char* op) {
+  dev(ref, "ref");
+  dev(rec, "rec");
+  same_device(ref, rec, "rec");
+  TORCH_CHECK_VALUE(ref.dim() == 2 && ref.size(0) > 0 && ref.size(1) > 0, "bigcodec::", op, ": ref must be a non-empty (B, T)");
+  TORCH_CHECK_VALUE(rec.sizes() == ref.sizes(), "bigcodec::", op, ": rec ", rec.sizes(), " != ref ", ref.sizes());
+}
+
+Tensor si_snr(const Tensor& ref, const Tensor& rec, const optional<Tensor>& lens) {
+  check_pair(ref, rec, "si_snr");
+  const int64_t B = ref.size(0);
+  const int* pl = opt_lens(ref, lens, B, "si_snr");
+  auto out = at::empty({B}, ref.options());
+  ok(bc_si_snr(ref.data_ptr<float>(), rec.data_ptr<float>(), pl, out.data_ptr<float>(), i32(B, "B"), ref.size(1),
+               stream_of(ref)),
+     "bc_si_snr");
+  return out;
+}
+
+Tensor logmel_l1(const Tensor& ref, const Tensor& rec, const optional<Tensor>& lens, const Tensor& basis,
+                 const Tensor& mel, int64_t n_fft, double clamp_eps) {
+  check_pair(ref, rec, "logmel_l1");
+  const int64_t B = ref.size(0), T = ref.size(1);
+  const int* pl = opt_lens(ref, lens, B, "logmel_l1");
+  TORCH_CHECK_VALUE(n_fft >= 16 && n_fft % 16 == 0 && n_fft <= (1 << 20), "bigcodec::logmel_l1: n_fft must be a multiple of 16");
+  const int64_t bins = n_fft / 2 + 1;
+  TORCH_CHECK_VALUE(basis.dim() == 2 && basis.size(0) == 2 * bins && basis.size(1) == n_fft,
+                    "bigcodec::logmel_l1: basis must be (2 * bins, n_fft) = (", 2 * bins, ", ", n_fft, ")");
+  TORCH_CHECK_VALUE(mel.dim() == 2 && mel.size(0) > 0 && mel.size(1) == bins,
+                    "bigcodec::logmel_l1: mel must be (n_mels, bins = ", bins, ")");
+  TORCH_CHECK_VALUE(clamp_eps > 0, "bigcodec::logmel_l1: clamp_eps must be positive");
+  const long long nws = bc_logmel_workspace_doubles(i32(B, "B"), T, (int)n_fft);
+  TORCH_CHECK_VALUE(nws > 0, "bigcodec::logmel_l1: unsupported batch shape");
+  auto ws = at::empty({(int64_t)nws}, ref.options().dtype(at::kDouble));
+  auto out = at::empty({B}, ref.options());
+  ok(bc_logmel_l1(ref.data_ptr<float>(), rec.data_ptr<float>(), pl, req(ref, basis, "basis"), req(ref, mel, "mel"),
+                  out.data_ptr<float>(), ws.data_ptr<double>(), (int)B, T, (int)n_fft, i32(mel.size(0), "n_mels"),
+                  (float)clamp_eps, stream_of(ref)),
+     "bc_logmel_l1");
+  return out;
+}
+
+void code_hist_(const Tensor& counts, const Tensor& codes, const optional<Tensor>& lens) {
+  dev(counts, "counts", at::kLong);
+  TORCH_CHECK_VALUE(counts.dim() == 1 && counts.numel() > 0, "bigcodec::code_hist_: counts must be (codebook_size,) int64");
+  TORCH_CHECK_VALUE(codes.is_cuda() && (codes.scalar_type() == at::kInt || codes.scalar_type() == at::kLong) &&
+                        codes.is_contiguous(),
+                    "bigcodec::code_hist_: codes must be a contiguous int32 / int64 device tensor");
+  same_device(counts, codes, "codes");
+  TORCH_CHECK_VALUE(codes.dim() == 2, "bigcodec::code_hist_: codes must be (B, T)");
+  const int* pl = opt_lens(counts, lens, codes.size(0), "code_hist_");
+  if (codes.numel() == 0) return;
+  ok(bc_code_hist(codes.data_ptr(), codes.scalar_type() == at::kLong ? 64 : 32, pl,
+                  reinterpret_cast<long long*>(counts.data_ptr<int64_t>()), i32(codes.size(0), "B"), codes.size(1),
+                  i32(counts.numel(), "codebook_size"), stream_of(counts)),
+     "bc_code_hist");
+}
+
 // Every op runs under a device guard of its first tensor argument (the data tensor), so the C ABI's launches
 // and the op's allocations land on that tensor's device even when it is not the current one (the ABI launches
 // on the current HIP device; c10 reports these tensors as "cuda", hence the masquerading guard).
@@ -524,6 +591,9 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("zero_tail_(Tensor(a!) y, Tensor(b!)? y2, Tensor lens, int tail_max) -> ()");
   m.def("resample_sinc(Tensor x, Tensor kern, int lout, int pitch, int orig, int new_freq, int taps, int width) -> Tensor");
   m.def("synth_clips_(Tensor(a!) x, int clip0) -> ()");
+  m.def("si_snr(Tensor ref, Tensor rec, Tensor? lens) -> Tensor");
+  m.def("logmel_l1(Tensor ref, Tensor rec, Tensor? lens, Tensor basis, Tensor mel, int n_fft, float clamp_eps) -> Tensor");
+  m.def("code_hist_(Tensor(a!) counts, Tensor codes, Tensor? lens) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
@@ -549,4 +619,7 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("zero_tail_", &Guarded<&zero_tail_>::call);
   m.impl("resample_sinc", &Guarded<&resample_sinc>::call);
   m.impl("synth_clips_", &Guarded<&synth_clips_>::call);
+  m.impl("si_snr", &Guarded<&si_snr>::call);
+  m.impl("logmel_l1", &Guarded<&logmel_l1>::call);
+  m.impl("code_hist_", &Guarded<&code_hist_>::call);
 }

@@ -26,7 +26,7 @@ _ns = None
 # every op the extension defines (tests check the registry against this list)
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
-       "zero_tail_")
+       "zero_tail_", "si_snr", "logmel_l1", "code_hist_")
 
 
 def load():
@@ -161,4 +161,16 @@ def _register_fakes():
 
     @reg("bigcodec::synth_clips_")
     def _synth(x, clip0):
+        return None
+
+    @reg("bigcodec::si_snr")
+    def _si_snr(ref, rec, lens):
+        return _new(ref, (ref.shape[0],))
+
+    @reg("bigcodec::logmel_l1")
+    def _logmel_l1(ref, rec, lens, basis, mel, n_fft, clamp_eps):
+        return _new(ref, (ref.shape[0],))
+
+    @reg("bigcodec::code_hist_")
+    def _code_hist(counts, codes, lens):
         return None

@@ -321,6 +321,33 @@ int bc_ctb_to_btc_add(const float* y, const float* skip, float* out, int B, int 
                       void* stream);
 int bc_synth_clips(float* x, int B, long long T, long long clip0, void* stream);
 
+/* ---- Round-trip quality metrics (added under ABI 18: additive, no existing entry point changes) -----------------
+ * What inference_full.py:570-604, 644-647, 723-737 reports of a reconstruction, where the waveforms already are
+ * (STOI and PESQ excepted: DESIGN.md section 16).  ref / rec are [B][T] fp32; lens[b] (int32, device; NULL = every
+ * clip fills T) is clip b's own length: samples at or beyond it are never read, and clip b's result is bit for bit
+ * what the clip alone gives.
+ * bc_si_snr: out[b] = torchmetrics' ScaleInvariantSignalNoiseRatio(preds = rec, target = ref) in dB over clip b:
+ *   t' = ref - mean, p' = rec - mean, eps = 2^-23, alpha = (sum p't' + eps) / (sum t't' + eps), s = alpha t',
+ *   10 log10((sum s^2 + eps) / (sum (s - p')^2 + eps)); three passes with fp64 accumulators (NaN for lens[b] <= 0).
+ * bc_logmel_l1: one resolution of criterions/mel_loss.py:22-31, 44-49 (torchaudio MelSpectrogram: periodic Hann
+ *   window of n_fft, hop n_fft / 4, center=True with reflect padding at the clip's own ends, one-sided magnitude,
+ *   mel matrix, clamp, log10): out[b] = mean over n_mels x (1 + lens[b] / hop) cells of
+ *   |log10 max(mel_ref, clamp_eps) - log10 max(mel_rec, clamp_eps)|.  basis[2 * bins][n_fft] (bins = n_fft / 2 + 1;
+ *   rows [0, bins) the windowed cosines, rows [bins, 2 bins) the windowed negative sines; 16-byte aligned) and
+ *   mel[n_mels][bins] are built on the host (audiotokenization_amd/metrics.py).  n_fft a multiple of 16,
+ *   n_mels <= 320 (else 3).  workspace: bc_logmel_workspace_doubles(B, T, n_fft) doubles (-1: bad arguments), one
+ *   partial sum per tile of bc_logmel_tile_frames() frames; no spectrogram is written to memory.  A clip shorter
+ *   than n_fft / 2 + 1 samples (reflect padding undefined) gives NaN.  Native fp32 MFMA operands.
+ * bc_code_hist: counts[c] (int64[n_codes], accumulated) += the number of codes[b][t] == c, t < lens[b] (in frames;
+ *   NULL = all T); codes (code_bits 32 or 64, signed) outside [0, n_codes) are ignored.  n_codes <= 16384 (else 3). */
+int bc_si_snr(const float* ref, const float* rec, const int* lens, float* out, int B, long long T, void* stream);
+int bc_logmel_tile_frames(void);
+long long bc_logmel_workspace_doubles(int B, long long T, int n_fft);
+int bc_logmel_l1(const float* ref, const float* rec, const int* lens, const float* basis, const float* mel, float* out,
+                 double* workspace, int B, long long T, int n_fft, int n_mels, float clamp_eps, void* stream);
+int bc_code_hist(const void* codes, int code_bits, const int* lens, long long* counts, int B, long long T, int n_codes,
+                 void* stream);
+
 /* ---- Bounds-checked debug build (no reference counterpart: SURVEY.md §5 row 2) ------------------------------
  * libbigcodec_hip.so built with -DBC_DEBUG (build_lib.build(debug=True) -> audiotokenization_amd/_debug/, loaded by
  * the Python package when BIGCODEC_DEBUG=1) checks the indices of the kernels' computed global accesses (conv /
