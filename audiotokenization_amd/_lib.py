@@ -62,6 +62,9 @@ _SIGS = {
     "bc_fsq_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "bc_fsq_codes": (I, [P, I, P, P, P, P, I, I, I, I, P]),
     "bc_stream_window": (I, [P, L, L, P, P, P, P, P, I, I, I, I, P]),
+    "bc_stream_window_slots": (I, [P, L, L, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "bc_lstm_state_gather": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "bc_lstm_state_scatter": (I, [P, P, P, P, P, I, I, I, I, P]),
     "bc_zero_tail": (I, [P, P, P, I, I, L, L, P]),
     "bc_resample_sinc": (I, [P, P, P, I, L, L, L, I, I, I, I, P]),
     "bc_rvq_update": (I, [P, P, P, L, I, P]),

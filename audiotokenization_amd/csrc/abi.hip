@@ -634,6 +634,23 @@ int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_s
                               n, P, S(stream));
 }
 
+int bc_stream_window_slots(const float* x, long long x_batch_stride, long long x_row_stride, float* pool, const int* src,
+                           const int* dst, const float* snake_alpha_exp, const float* snake_inv_beta, float* win, int B,
+                           int C, int n, int P, int pool_rows, void* stream) {
+  return stream_window_slots_launch(x, x_batch_stride, x_row_stride, pool, src, dst, snake_alpha_exp, snake_inv_beta, win,
+                                    B, C, n, P, pool_rows, S(stream));
+}
+
+int bc_lstm_state_gather(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0, int num_layers,
+                         int H, int B, int pool_rows, void* stream) {
+  return lstm_state_gather_launch(h_pool, c_pool, src, h0, c0, num_layers, H, B, pool_rows, S(stream));
+}
+
+int bc_lstm_state_scatter(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT, int num_layers,
+                          int H, int B, int pool_rows, void* stream) {
+  return lstm_state_scatter_launch(h_pool, c_pool, dst, hT, cT, num_layers, H, B, pool_rows, S(stream));
+}
+
 int bc_zero_tail(float* y, float* y2, const int* lens, int B, int C, long long T, long long tail_max, void* stream) {
   if (!y || !lens || B <= 0 || C <= 0 || T <= 0) return BC_ERR_ARG;
   if (tail_max <= 0) return BC_OK;

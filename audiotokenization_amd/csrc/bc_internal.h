@@ -92,6 +92,13 @@ int snake_launch(const float* x, const float* sa, const float* sb, float* y, int
                  long long T, hipStream_t st);
 int stream_window_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa, const float* sb,
                          float* win, float* ctx_out, int B, int C, int n, int P, hipStream_t st);
+int stream_window_slots_launch(const float* x, long long xbs, long long xT, float* pool, const int* src, const int* dst,
+                               const float* sa, const float* sb, float* win, int B, int C, int n, int P, int pool_rows,
+                               hipStream_t st);
+int lstm_state_gather_launch(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0,
+                             int num_layers, int H, int B, int pool_rows, hipStream_t st);
+int lstm_state_scatter_launch(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT,
+                              int num_layers, int H, int B, int pool_rows, hipStream_t st);
 int zero_tail_launch(float* y, float* y2, const int* lens, int B, int C, long long T, long long tail_max, hipStream_t st);
 int aa_snake_launch(const float* x, const float* sa, const float* sb, const float* fu,
                     const float* fd, float* y, int B, int C, int T, hipStream_t st);

@@ -11,6 +11,8 @@
 //  transpose kernels: [B][C][T] <-> [C][T][B] layouts around the ResLSTM (vq/module.py:160-166).
 //  synth_clips      : counter-hash white noise generated in HBM.
 //  stream_window    : a causal stream's [carried context | chunk] window (+ Snake) and its next context.
+//  stream_window_slots / lstm_state_gather / lstm_state_scatter : the same step for a pool of independent sessions,
+//                     the carried state indexed by per-entry pool rows (streaming.py StreamPool).
 //  zero_tail        : zeros from each clip's own length to the padded end of a ragged batch's rows.
 #include <algorithm>
 #include "bc_common.h"
@@ -232,6 +234,125 @@ int stream_window_launch(const float* x, long long xbs, long long xT, const floa
   const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
   hipLaunchKernelGGL(stream_window_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, ctx, sa, sb, win, ctx_out, C, n,
                      P, (int)rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
+// Streaming session pool (streaming.py StreamPool): stream_window_kernel with the contexts of many independent
+// sessions in a pool[pool_rows][C][P] and two device index arrays: entry b of a push reads its context from pool row
+// src[b] (src[b] < 0: a fresh session, zeros) and stores its next context to pool row dst[b] (dst[b] < 0: not stored,
+// the padding entries of a graph replay).  Same window, same snake(), same strided x.
+// IN-PLACE HAZARD: with n < P, context element i of a row is read by the thread that writes window column i and
+// overwritten by the thread at column n + i, which may sit in another workgroup, so a row must never be read and
+// written in one launch.  The HOST guarantees it: the src and dst row sets of a launch are disjoint and dst holds no
+// row twice (StreamPool's ping-pong rows 2s / 2s + 1 per session); the kernel cannot check it.
+// Same 2-D grid and 32-bit row arithmetic as stream_window_kernel.
+__global__ void __launch_bounds__(256) stream_window_slots_kernel(const float* __restrict__ x, long long xbs, long long xT,
+                                                                  float* pool, const int* __restrict__ src,
+                                                                  const int* __restrict__ dst, const float* __restrict__ sa,
+                                                                  const float* __restrict__ sb, float* __restrict__ win,
+                                                                  int C, int n, int P, int rows, int pool_rows) {
+  const int W = P + n;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = row / C, c = row - b * C;
+    const int s = src[b], d = dst[b];
+    const float* xr = x + (long long)b * xbs + (long long)c * xT;
+    float* wr = win + (long long)row * W;
+    // (the slot values come from device memory: the debug build checks them against the pool, a bad one is skipped)
+    const float* cr = (s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * P : nullptr;
+    float* nr = (d >= 0 && BC_DOK(d < pool_rows)) ? pool + ((long long)d * C + c) * P : nullptr;
+    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
+      float v;
+      if (j < P) {
+        v = cr ? cr[j] : 0.f;
+      } else {
+        v = xr[j - P];
+        if (sa) v = snake(v, a_, b_);
+      }
+      wr[j] = v;
+      if (j >= n && nr) nr[j - n] = v;
+    }
+  }
+}
+
+int stream_window_slots_launch(const float* x, long long xbs, long long xT, float* pool, const int* src, const int* dst,
+                               const float* sa, const float* sb, float* win, int B, int C, int n, int P, int pool_rows,
+                               hipStream_t st) {
+  if (!x || !pool || !src || !dst || !win || B < 0 || C < 1 || n < 1 || P < 1 || pool_rows < 1) return BC_ERR_ARG;
+  if (xT < n || xbs < (long long)(C - 1) * xT + n || (sa == nullptr) != (sb == nullptr)) return BC_ERR_ARG;
+  const long long rows = (long long)B * C, W = (long long)P + n;
+  if (rows > 0x7fffffffLL || W > 0x7fffffffLL || (long long)pool_rows * C > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
+  if (rows == 0) return BC_OK;
+  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
+  hipLaunchKernelGGL(stream_window_slots_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, pool, src, dst, sa, sb, win,
+                     C, n, P, (int)rows, pool_rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
+// The carried ResLSTM state of a session pool: bc_reslstm_fwd_state takes dense [num_layers][H][B] (unit-major) h0 / c0
+// and hands back hT / cT; the pool keeps [num_layers][H][pool_rows].  Gather: h0[lu][b] = src[b] >= 0 ?
+// h_pool[lu][src[b]] : 0 (a fresh session's zero state), c likewise; scatter: h_pool[lu][dst[b]] = hT[lu][b] for
+// dst[b] >= 0.  lu walks the LH = num_layers * H units; h and c in one launch.
+__global__ void __launch_bounds__(256) lstm_state_gather_kernel(const float* __restrict__ h_pool,
+                                                                const float* __restrict__ c_pool,
+                                                                const int* __restrict__ src, float* __restrict__ h0,
+                                                                float* __restrict__ c0, int LH, int B, int pool_rows) {
+  const int total = LH * B;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    const int lu = e / B, b = e - lu * B;
+    const int s = src[b];
+    const bool live = s >= 0 && BC_DOK(s < pool_rows);
+    const long long i = (long long)lu * pool_rows + s;
+    h0[e] = live ? h_pool[i] : 0.f;
+    c0[e] = live ? c_pool[i] : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(256) lstm_state_scatter_kernel(float* __restrict__ h_pool, float* __restrict__ c_pool,
+                                                                 const int* __restrict__ dst,
+                                                                 const float* __restrict__ hT,
+                                                                 const float* __restrict__ cT, int LH, int B,
+                                                                 int pool_rows) {
+  const int total = LH * B;
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+    const int lu = e / B, b = e - lu * B;
+    const int d = dst[b];
+    if (d < 0 || !BC_DOK(d < pool_rows)) continue;
+    const long long i = (long long)lu * pool_rows + d;
+    h_pool[i] = hT[e];
+    c_pool[i] = cT[e];
+  }
+}
+
+static int lstm_state_sizes(int num_layers, int H, int B, int pool_rows, long long* total) {
+  if (num_layers < 1 || H < 1 || B < 0 || pool_rows < 1) return BC_ERR_ARG;
+  *total = (long long)num_layers * H * B;
+  if ((long long)num_layers * H > 0x7fffffffLL || *total > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
+  return BC_OK;
+}
+
+int lstm_state_gather_launch(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0,
+                             int num_layers, int H, int B, int pool_rows, hipStream_t st) {
+  long long total = 0;
+  if (!h_pool || !c_pool || !src || !h0 || !c0) return BC_ERR_ARG;
+  if (const int rc = lstm_state_sizes(num_layers, H, B, pool_rows, &total)) return rc;
+  if (total == 0) return BC_OK;
+  hipLaunchKernelGGL(lstm_state_gather_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, h_pool, c_pool, src, h0, c0,
+                     num_layers * H, B, pool_rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
+int lstm_state_scatter_launch(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT,
+                              int num_layers, int H, int B, int pool_rows, hipStream_t st) {
+  long long total = 0;
+  if (!h_pool || !c_pool || !dst || !hT || !cT) return BC_ERR_ARG;
+  if (const int rc = lstm_state_sizes(num_layers, H, B, pool_rows, &total)) return rc;
+  if (total == 0) return BC_OK;
+  hipLaunchKernelGGL(lstm_state_scatter_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, h_pool, c_pool, dst, hT, cT,
+                     num_layers * H, B, pool_rows);
   BC_CHECK_LAUNCH();
   return BC_OK;
 }

@@ -403,6 +403,76 @@ std::vector<Tensor> stream_window(const Tensor& x, const optional<Tensor>& ctx, 
   return {win, nctx};
 }
 
+// ---- the streaming session pool: stream_window over pool rows, and the ResLSTM state gather / scatter ----------
+const int* slots(const Tensor& ref, const Tensor& t, int64_t B, const char* op, const char* name) {
+  dev(t, name, at::kInt);
+  same_device(ref, t, name);
+  TORCH_CHECK_VALUE(t.dim() == 1 && t.size(0) == B, "bigcodec::", op, ": ", name, " must be (", B, ",) int32, one pool row per entry");
+  return t.data_ptr<int>();
+}
+
+Tensor stream_window_slots_(const Tensor& x, const Tensor& pool, const Tensor& src, const Tensor& dst,
+                            const optional<Tensor>& a, const optional<Tensor>& ib, int64_t P) {
+  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && x.stride(2) == 1,
+                    "bigcodec::stream_window_slots_: x must be a (B, C, n) float32 tensor with unit time stride");
+  const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
+  TORCH_CHECK_VALUE(P >= 1 && n >= 1, "bigcodec::stream_window_slots_: P >= 1 and a non-empty chunk");
+  check_coeffs(a, ib, C, "stream_window_slots_");
+  dev(pool, "pool");
+  same_device(x, pool, "pool");
+  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && pool.size(2) == P,
+                    "bigcodec::stream_window_slots_: pool must be (rows, C, P)");
+  const int* ps = slots(x, src, B, "stream_window_slots_", "src");
+  const int* pd = slots(x, dst, B, "stream_window_slots_", "dst");
+  auto win = at::empty({B, C, P + n}, x.options());
+  if (B == 0) return win;
+  ok(bc_stream_window_slots(x.data_ptr<float>(), B > 1 ? x.stride(0) : C * x.stride(1), C > 1 ? x.stride(1) : n,
+                            pool.data_ptr<float>(), ps, pd, optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
+                            win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(P, "P"),
+                            i32(pool.size(0), "pool rows"), stream_of(x)),
+     "bc_stream_window_slots");
+  return win;
+}
+
+std::vector<Tensor> lstm_state_gather(const Tensor& h_pool, const Tensor& c_pool, const Tensor& src, int64_t B) {
+  dev(h_pool, "h_pool");
+  dev(c_pool, "c_pool");
+  same_device(h_pool, c_pool, "c_pool");
+  TORCH_CHECK_VALUE(h_pool.dim() == 3 && h_pool.size(2) >= 1 && c_pool.sizes() == h_pool.sizes(),
+                    "bigcodec::lstm_state_gather: h_pool and c_pool must both be (layers, H, rows)");
+  TORCH_CHECK_VALUE(B >= 0, "bigcodec::lstm_state_gather: B >= 0");
+  const int* ps = slots(h_pool, src, B, "lstm_state_gather", "src");
+  const int64_t L = h_pool.size(0), H = h_pool.size(1);
+  auto h0 = at::empty({L, H, B}, h_pool.options());
+  auto c0 = at::empty({L, H, B}, h_pool.options());
+  if (h0.numel() == 0) return {h0, c0};
+  ok(bc_lstm_state_gather(h_pool.data_ptr<float>(), c_pool.data_ptr<float>(), ps, h0.data_ptr<float>(),
+                          c0.data_ptr<float>(), i32(L, "layers"), i32(H, "H"), i32(B, "B"), i32(h_pool.size(2), "pool rows"),
+                          stream_of(h_pool)),
+     "bc_lstm_state_gather");
+  return {h0, c0};
+}
+
+void lstm_state_scatter_(const Tensor& h_pool, const Tensor& c_pool, const Tensor& hT, const Tensor& cT,
+                         const Tensor& dst) {
+  dev(h_pool, "h_pool");
+  dev(c_pool, "c_pool");
+  same_device(h_pool, c_pool, "c_pool");
+  TORCH_CHECK_VALUE(h_pool.dim() == 3 && h_pool.size(2) >= 1 && c_pool.sizes() == h_pool.sizes(),
+                    "bigcodec::lstm_state_scatter_: h_pool and c_pool must both be (layers, H, rows)");
+  const float* ph = req(h_pool, hT, "hT");
+  const float* pc = req(h_pool, cT, "cT");
+  TORCH_CHECK_VALUE(hT.dim() == 3 && hT.size(0) == h_pool.size(0) && hT.size(1) == h_pool.size(1) && cT.sizes() == hT.sizes(),
+                    "bigcodec::lstm_state_scatter_: hT and cT must both be (layers, H, B)");
+  const int64_t B = hT.size(2);
+  const int* pd = slots(h_pool, dst, B, "lstm_state_scatter_", "dst");
+  if (hT.numel() == 0) return;
+  ok(bc_lstm_state_scatter(h_pool.data_ptr<float>(), c_pool.data_ptr<float>(), pd, ph, pc, i32(h_pool.size(0), "layers"),
+                           i32(h_pool.size(1), "H"), i32(B, "B"), i32(h_pool.size(2), "pool rows"), stream_of(h_pool)),
+     "bc_lstm_state_scatter");
+}
+
 // ---- zero_tail_: the zero tails of a ragged batch (each clip's own length to the padded end) -------------------
 void zero_tail_(const Tensor& y, const optional<Tensor>& y2, const Tensor& lens, int64_t tail_max) {
   dev(y, "y");
@@ -588,6 +658,10 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("fsq(Tensor z, Tensor w_in, Tensor b_in, Tensor w_out, Tensor b_out, Tensor consts) -> Tensor[]");
   m.def("fsq_codes(Tensor idx, Tensor w_out, Tensor b_out, int[] levels) -> Tensor");
   m.def("stream_window(Tensor x, Tensor? ctx, Tensor? alpha_exp, Tensor? inv_beta, int P) -> Tensor[]");
+  m.def("stream_window_slots_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor? alpha_exp, Tensor? inv_beta, "
+        "int P) -> Tensor");
+  m.def("lstm_state_gather(Tensor h_pool, Tensor c_pool, Tensor src, int B) -> Tensor[]");
+  m.def("lstm_state_scatter_(Tensor(a!) h_pool, Tensor(b!) c_pool, Tensor hT, Tensor cT, Tensor dst) -> ()");
   m.def("zero_tail_(Tensor(a!) y, Tensor(b!)? y2, Tensor lens, int tail_max) -> ()");
   m.def("resample_sinc(Tensor x, Tensor kern, int lout, int pitch, int orig, int new_freq, int taps, int width) -> Tensor");
   m.def("synth_clips_(Tensor(a!) x, int clip0) -> ()");
@@ -616,6 +690,9 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("fsq", &Guarded<&fsq>::call);
   m.impl("fsq_codes", &Guarded<&fsq_codes>::call);
   m.impl("stream_window", &Guarded<&stream_window>::call);
+  m.impl("stream_window_slots_", &Guarded<&stream_window_slots_>::call);
+  m.impl("lstm_state_gather", &Guarded<&lstm_state_gather>::call);
+  m.impl("lstm_state_scatter_", &Guarded<&lstm_state_scatter_>::call);
   m.impl("zero_tail_", &Guarded<&zero_tail_>::call);
   m.impl("resample_sinc", &Guarded<&resample_sinc>::call);
   m.impl("synth_clips_", &Guarded<&synth_clips_>::call);

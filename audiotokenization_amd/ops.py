@@ -26,7 +26,7 @@ _ns = None
 # every op the extension defines (tests check the registry against this list)
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
-       "zero_tail_", "si_snr", "logmel_l1", "code_hist_")
+       "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_")
 
 
 def load():
@@ -150,6 +150,20 @@ def _register_fakes():
     def _stream_window(x, ctx, a, ib, P):
         B, C, n = x.shape
         return [_new(x, (B, C, P + n)), _new(x, (B, C, P))]
+
+    @reg("bigcodec::stream_window_slots_")
+    def _stream_window_slots(x, pool, src, dst, a, ib, P):
+        B, C, n = x.shape
+        return _new(x, (B, C, P + n))
+
+    @reg("bigcodec::lstm_state_gather")
+    def _lstm_state_gather(h_pool, c_pool, src, B):
+        shape = (h_pool.shape[0], h_pool.shape[1], B)
+        return [_new(h_pool, shape), _new(h_pool, shape)]
+
+    @reg("bigcodec::lstm_state_scatter_")
+    def _lstm_state_scatter(h_pool, c_pool, hT, cT, dst):
+        return None
 
     @reg("bigcodec::resample_sinc")
     def _resample(x, kern, lout, pitch, orig, new_freq, taps, width):

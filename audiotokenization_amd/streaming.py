@@ -26,6 +26,12 @@ frames in, waveform out.  Its upsamplers are CausalConvTranspose1d (vq/module.py
 k = 2s, stride s, no padding, the last s outputs cropped), so output block t depends on input frames t and t - 1:
 each carries its last input frame and runs the chunk over [frame | chunk] with padding s (which drops the s
 outputs of the carried frame's own block on the left and the k - s look-ahead outputs on the right).
+
+StreamPool serves many independent sessions, which open, close and skip ticks on their own, with one
+batched push: the same stages on a batch of whichever sessions are live, the carried state in per-stage pools on the
+device and indexed by slot (bc_stream_window_slots, bc_lstm_state_gather / bc_lstm_state_scatter).  Sessions in one
+push share the chunk length: a chunk length per session would need the persistent ResLSTM to hand back its state at
+each clip's own last step.
 """
 from __future__ import annotations
 
@@ -211,6 +217,286 @@ class StreamingDecoder(StreamingEncoder):
         self.reset()
         outs = [self.push(z[..., i:i + chunk]) for i in range(0, z.shape[-1], chunk)]
         return torch.cat(outs, dim=2)
+
+
+def plan_rows(entries):
+    """The (src, dst) pool rows of one pool push, from (slot, pushes so far) per entry.  A session's state is
+    ping-pong: slot s owns rows 2s and 2s + 1; its push number k reads row 2s + (k & 1) (k == 0: -1, a fresh session
+    reads zeros) and writes row 2s + ((k + 1) & 1).  With distinct slots the two row sets are disjoint and dst holds
+    no row twice, which is what bc_stream_window_slots needs (include/bigcodec.h).  Pure host arithmetic."""
+    src = [2 * s + (k & 1) if k else -1 for s, k in entries]
+    dst = [2 * s + ((k + 1) & 1) for s, k in entries]
+    return src, dst
+
+
+class SlotTable:
+    """The host side of a StreamPool: which slots are open, how many pushes each session has made (its ping-pong
+    phase), its sample count, and which sessions a failed push left undefined.  A session id is its slot number."""
+
+    def __init__(self, capacity: int):
+        if int(capacity) < 1:
+            raise ValueError(f"a session pool needs a capacity of at least 1 (got {capacity})")
+        self.capacity = int(capacity)
+        self.pushes = [None] * self.capacity  # None: the slot is free
+        self.samples = [0] * self.capacity
+        self.undefined = set()
+
+    def open(self) -> int:
+        for s, k in enumerate(self.pushes):
+            if k is None:
+                self.pushes[s], self.samples[s] = 0, 0
+                return s
+        raise RuntimeError(f"the session pool is full ({self.capacity} sessions open)")
+
+    def close(self, sid) -> None:
+        self.check([sid], self.capacity, allow_undefined=True)
+        self.pushes[sid] = None
+        self.undefined.discard(sid)
+
+    def live(self):
+        return [s for s, k in enumerate(self.pushes) if k is not None]
+
+    def check(self, sids, most: int, allow_undefined: bool = False):
+        """The session ids of one push as a list, or ValueError: empty, more than `most`, unknown or closed, twice in
+        one push (two writers of one pool row); RuntimeError for a session an earlier failed push left undefined."""
+        sids = list(sids)
+        if not sids:
+            raise ValueError("a pool push needs at least one session")
+        if len(sids) > most:
+            raise ValueError(f"{len(sids)} sessions in one push: at most {most}")
+        for s in sids:
+            if isinstance(s, bool) or not isinstance(s, int) or not 0 <= s < self.capacity or self.pushes[s] is None:
+                raise ValueError(f"session {s!r} is not open in this pool")
+        if len(set(sids)) != len(sids):
+            raise ValueError(f"a session appears twice in one push: {sids}")
+        bad = [s for s in sids if s in self.undefined]
+        if bad and not allow_undefined:
+            raise RuntimeError(f"sessions {bad} were in a push that failed: their state is undefined, close them")
+        return sids
+
+    def plan(self, sids):
+        return plan_rows([(s, self.pushes[s]) for s in sids])
+
+    def commit(self, sids, samples: int) -> None:
+        for s in sids:
+            self.pushes[s] += 1
+            self.samples[s] += samples
+
+
+class _PoolState:
+    """The two places a stream touches its carried state, for a pool: the contexts of a stage live in one
+    (2 * capacity, C, P) tensor and the ResLSTM state in two (layers, H, 2 * capacity) tensors, allocated at the
+    stage's first push and never zeroed (a fresh session reads zeros through src = -1), and the current push's
+    device index arrays `_src` / `_dst` (int32, one pool row per entry) say which rows it reads and writes."""
+
+    _rows = 0
+    _src = _dst = None
+
+    def _window(self, key, x, P: int, act=None):
+        if not P:  # no history, no state: the plain window (a dense copy of a strided view, or the Snake alone)
+            return super()._window(key, x, P, act)
+        sa, sb = act.act.coeffs(x.device) if act is not None else (None, None)
+        pool = self._ctx.get(key)
+        if pool is None:
+            pool = self._ctx[key] = torch.empty(self._rows, x.shape[1], P, device=x.device, dtype=torch.float32)
+        return ops.load().stream_window_slots_(x, pool, self._src, self._dst, sa, sb, P)
+
+    def _lstm_run(self, m: ResLSTM, h):
+        ns = ops.load()
+        pools = self._lstm.get(id(m))
+        if pools is None:
+            shape = (m.lstm.num_layers, h.shape[1], self._rows)
+            pools = self._lstm[id(m)] = tuple(torch.empty(shape, device=h.device, dtype=torch.float32) for _ in "hc")
+        h0, c0 = ns.lstm_state_gather(pools[0], pools[1], self._src, h.shape[0])
+        y, (hT, cT) = m.run(h, state=(h0, c0), return_state=True)
+        ns.lstm_state_scatter_(pools[0], pools[1], hT, cT, self._dst)
+        return y
+
+
+class _PoolEncoder(_PoolState, StreamingEncoder):
+    pass
+
+
+class _PoolDecoder(_PoolState, StreamingDecoder):
+    pass
+
+
+class StreamPool:
+    """Many independent causal streams in one batched push: a pool of per-session state on the device.
+
+        pool = StreamPool(model, capacity)   # a causal BigCodecEncoder or BigCodecDecoder (StreamingEncoder's refusals)
+        sid = pool.open()                    # the lowest free slot; RuntimeError when the pool is full
+        y = pool.push(sids, x)               # x (len(sids), 1, n) samples / (len(sids), D, n) frames: row i is sids[i]'s
+        wav = pool.tokens(sids, codes)       # decoder pools: codes (len(sids), n, Nq) int64 on the device
+        pool.close(sid)                      # the slot is free again; nothing is zeroed
+
+    Each session gets exactly what its own B = 1 StreamingEncoder / StreamingDecoder would have produced (bit for bit
+    in x6; to fp32 rounding in h3, whose block scales depend on the tiling), whatever else is in the push: sessions
+    open, close and sit out ticks independently, the order of `sids` is free, and the chunk length n (a multiple of the
+    hop; one n per call) may differ between calls.  The push runs StreamingEncoder's / StreamingDecoder's own stages on
+    the batch; only the state access differs: one bc_stream_window_slots launch per stage that carries history, one
+    bc_lstm_state_gather and one bc_lstm_state_scatter per ResLSTM, all indexed by one (src, dst) pair of pool rows
+    per entry (plan_rows: ping-pong rows, so no launch reads a row it writes).  The pair is built on the host, written
+    to pinned memory and copied without a wait; no torch compute kernel runs in a push.
+
+    Refused on the host before any launch: an unknown, closed or repeated session id, an empty push, a batch
+    dimension other than len(sids), a chunk that is no multiple of the hop (ValueError); a precision other than the
+    one of the pool's first push (RuntimeError).  When a push raises later than that, launches may have been queued
+    and the state of ITS sessions is undefined: further pushes for them raise RuntimeError until they are closed."""
+
+    def __init__(self, model, capacity: int):
+        self.table = SlotTable(capacity)
+        self.decoder = hasattr(model, "tokens_to_latent")
+        self._stream = (_PoolDecoder if self.decoder else _PoolEncoder)(model)
+        self._stream._rows = 2 * self.table.capacity
+        self.capacity, self.hop = self.table.capacity, self._stream.hop
+        conv0 = _conv_of((model.model if self.decoder else model.block)[0])
+        self.channels = int(conv0.in_channels)  # of a push's input: 1 (samples) or the latent width
+        self._started = False
+        self._pinned = self._event = None
+
+    # ---- sessions ------------------------------------------------------------------------------------------------
+    def open(self) -> int:
+        return self.table.open()
+
+    def close(self, sid) -> None:
+        self.table.close(sid)
+
+    def live(self):
+        """The open session ids, ascending."""
+        return self.table.live()
+
+    def samples(self, sid) -> int:
+        """Samples session `sid` has consumed (encoder pools) or produced (decoder pools) so far."""
+        self.table.check([sid], 1, allow_undefined=True)
+        return self.table.samples[sid]
+
+    def state_bytes(self) -> int:
+        """Bytes of device state the pool holds (both ping-pong rows of every slot; 0 before the first push)."""
+        s = self._stream
+        return sum(t.numel() * 4 for t in s._ctx.values()) + sum(t.numel() * 4 for v in s._lstm.values() for t in v)
+
+    # ---- pushes --------------------------------------------------------------------------------------------------
+    def _admit(self, sids, shape, most=None, channels=None):
+        """Every host-side refusal of a push (nothing is launched before it passes); returns the ids as a list."""
+        sids = self.table.check(sids, most or self.capacity)
+        channels = self.channels if channels is None else channels
+        if len(shape) != 3 or shape[0] != len(sids):
+            raise ValueError(f"input of shape {tuple(shape)} for {len(sids)} sessions: row i belongs to sids[i]")
+        if channels and shape[1] != channels:
+            raise ValueError(f"input of shape {tuple(shape)}: expected {channels} channels")
+        if shape[2] < 1 or (not self.decoder and shape[2] % self.hop):
+            raise ValueError(f"chunk of {shape[2]} samples: must be a positive multiple of the hop ({self.hop})")
+        if self._started:
+            self._stream._check_mode()
+        return sids
+
+    def _start(self) -> None:
+        if not self._started:  # the precision the pool's state belongs to is the one of its first push
+            self._stream._mode, self._started = _lib.precision_mode(), True
+
+    def _stage(self, rows, out) -> None:
+        """`rows` (src then dst) into the device tensor `out`: pinned staging and a copy the host does not wait for
+        (the wait on the previous copy's event has nothing left to wait for once that push's status was read)."""
+        if self._pinned is None or self._pinned.numel() < len(rows):
+            self._pinned = torch.empty(max(len(rows), 2 * self.capacity), dtype=torch.int32, pin_memory=out.is_cuda)
+            self._event = torch.cuda.Event() if out.is_cuda else None
+        elif self._event is not None:
+            self._event.synchronize()
+        self._pinned[:len(rows)] = torch.tensor(rows, dtype=torch.int32)
+        out.copy_(self._pinned[:len(rows)], non_blocking=True)
+        if self._event is not None:
+            self._event.record(torch.cuda.current_stream(out.device))
+
+    def push(self, sids, x) -> torch.Tensor:
+        sids = self._admit(sids, x.shape)
+        src, dst = self.table.plan(sids)
+        self._start()
+        s = self._stream
+        try:
+            x = _as_input(x)
+            idx = torch.empty(2 * len(sids), dtype=torch.int32, device=x.device)
+            self._stage(src + dst, idx)
+            s._src, s._dst = idx[:len(sids)], idx[len(sids):]
+            y = s.push(x)
+        except BaseException:
+            self.table.undefined.update(sids)
+            raise
+        self.table.commit(sids, y.shape[-1] if self.decoder else x.shape[-1])
+        return y
+
+    def tokens(self, sids, codes) -> torch.Tensor:
+        """codes (len(sids), n, Nq) int64 on the device -> waveform chunks (len(sids), 1, n * hop)."""
+        if not self.decoder:
+            raise TypeError("tokens() needs a pool over a decoder")
+        self._admit(sids, (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape, channels=0)
+        return self.push(sids, self._stream.decoder.tokens_to_latent(codes))
+
+    def graph(self, B: int, n: int) -> "PoolGraph":
+        """One pool push of up to B sessions and chunks of n samples (encoder) / frames (decoder) as a HIP graph."""
+        return PoolGraph(self, B, n)
+
+
+class PoolGraph:
+    """A pool push of B entries of chunk length n captured in a HIP graph (as StreamGraph captures a stream's).  The
+    input and the (src, dst) index arrays are static tensors and the pools themselves are the static state: the
+    captured kernels write them in place, so there are no copy-back nodes, eager pushes and replays of the same pool
+    mix freely, and ONE graph serves any membership: push(sids, x) takes len(sids) <= B sessions, pads the missing
+    entries with src = dst = -1 (they read zeros and store nothing) and zero input, replays, and returns the first
+    len(sids) rows of the static output (overwritten by the next push: copy it to keep it).  check as in StreamGraph."""
+
+    def __init__(self, pool: StreamPool, B: int, n: int):
+        B, n = int(B), int(n)
+        if not 1 <= B <= pool.capacity:
+            raise ValueError(f"a graph of {B} entries on a pool of capacity {pool.capacity}")
+        if n < 1 or (not pool.decoder and n % pool.hop):
+            raise ValueError(f"chunk of {n} samples: must be a positive multiple of the hop ({pool.hop})")
+        self.pool, self.B = pool, B
+        if pool._started:
+            pool._stream._check_mode()
+        pool._start()
+        s = pool._stream
+        dev = next(p for p in (s.decoder if pool.decoder else s.encoder).parameters()).device
+        self.input = torch.zeros(B, pool.channels, n, device=dev)
+        self._dirty = 0  # rows of the static input that hold a session's data
+        self._idx = torch.full((2 * B,), -1, dtype=torch.int32, device=dev)
+        s._src, s._dst = self._idx[:B], self._idx[B:]
+        # one eager push of padding entries allocates every pool and warms the weight caches; it stores no state
+        with torch.no_grad():
+            s.push(self.input)
+        torch.cuda.synchronize()
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.no_grad(), _lib.deferred_status() as ticket:
+            with torch.cuda.graph(self._graph):
+                self.output = s.push(self.input)
+        self._status = ticket.items  # the graph's own status words, rewritten by every replay
+
+    def push(self, sids, x, check: bool = True) -> torch.Tensor:
+        pool = self.pool
+        sids = pool._admit(sids, x.shape, most=self.B)
+        if x.shape[2] != self.input.shape[2]:
+            raise ValueError(f"this graph was captured for chunks of {self.input.shape[2]}, got {x.shape[2]}")
+        src, dst = pool.table.plan(sids)
+        m, pad = len(sids), [-1] * (self.B - len(sids))
+        try:
+            pool._stage(src + pad + dst + pad, self._idx)
+            self.input[:m].copy_(_as_input(x))
+            if self._dirty > m:
+                self.input[m:self._dirty].zero_()
+            self._dirty = m
+            self._graph.replay()
+            if check:
+                self.check()
+        except BaseException:
+            pool.table.undefined.update(sids)
+            raise
+        pool.table.commit(sids, self.output.shape[-1] if pool.decoder else x.shape[-1])
+        return self.output[:m]
+
+    def check(self) -> None:
+        """Raise BigCodecLibraryError if the last replay's persistent ResLSTM reported a failure (host wait)."""
+        if self._status:
+            _lib._raise_bad(self._status, torch.cat([t.reshape(-1) for t, _ in self._status]).cpu().tolist())
 
 
 class StreamGraph:

@@ -280,6 +280,29 @@ int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_s
                      const float* snake_alpha_exp, const float* snake_inv_beta, float* win, float* ctx_out, int B, int C,
                      int n, int P, void* stream);
 
+/* bc_stream_window_slots: bc_stream_window for a pool of independent streaming sessions (streaming.py StreamPool).  It
+ *   stands in for no reference behaviour: the reference has no streaming, and its whole-sequence causal pass defines
+ *   each session's result, as for bc_stream_window.  The contexts live in pool[pool_rows][C][P]; the DEVICE arrays
+ *   src[B] / dst[B] give, for entry b of the push, the pool row its context is read from (src[b] < 0: a fresh session,
+ *   zeros) and the row the next context (the window's last P columns) is stored to (dst[b] < 0: not stored, a
+ *   padding entry).  win [B][C][P + n], x, the Snake and the strides as in bc_stream_window (bit-identical values);
+ *   P >= 1 (a stage without history has no state: bc_stream_window).  With n < P a row's elements are read and
+ *   overwritten by different workgroups, so the CALLER guarantees that no row is both in src and in dst of one call
+ *   and that dst names no row twice; slot values are not checked by the launcher (they are on the device; the debug
+ *   build skips and counts a row >= pool_rows).  Returns 1 for a null pointer or inconsistent sizes, 3 when B * C,
+ *   P + n or pool_rows * C exceeds 2^31 - 1, 0 without a launch when B == 0.
+ * bc_lstm_state_gather / bc_lstm_state_scatter: the pool's ResLSTM state around bc_reslstm_fwd_state (which still sees
+ *   a dense batch).  h_pool / c_pool are [num_layers][H][pool_rows], h0 / c0 / hT / cT [num_layers][H][B].  Gather:
+ *   h0[l][u][b] = src[b] < 0 ? 0 : h_pool[l][u][src[b]] (c likewise); scatter: h_pool[l][u][dst[b]] = hT[l][u][b] for
+ *   dst[b] >= 0 (dst without duplicates).  One launch serves h and c.  Same status codes. */
+int bc_stream_window_slots(const float* x, long long x_batch_stride, long long x_row_stride, float* pool, const int* src,
+                           const int* dst, const float* snake_alpha_exp, const float* snake_inv_beta, float* win, int B,
+                           int C, int n, int P, int pool_rows, void* stream);
+int bc_lstm_state_gather(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0, int num_layers,
+                         int H, int B, int pool_rows, void* stream);
+int bc_lstm_state_scatter(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT, int num_layers,
+                          int H, int B, int pool_rows, void* stream);
+
 /* bc_zero_tail (ABI 18): ragged batches (clips of different lengths zero-padded into one batch; the reference encodes
  *   each file alone, extract_indices.py:497-561, and its convs zero-pad at the clip's end, vq/module.py:45-48, 59-72).
  *   For y[B][C][T], the optional y2 of the same shape (NULL: none) and the DEVICE array lens[B], stores 0.0f at every

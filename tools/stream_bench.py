@@ -7,6 +7,8 @@ around the whole stream), ms per push and the number of kernel launches per push
 --graph replays one captured HIP graph per chunk (StreamGraph; status words read once at the end).
 --prev times the round-4 first-session stream (tools/lab/streaming_prev.py: separate Snake launches, torch.cat
 contexts, two-launch ResidualUnits) on the same models for an A/B.  Random weights, synthetic white noise.
+--pool [--decode] [--pool-B 16 64] [--pool-frames 1 5] times a tick of B independent sessions through the session
+pool (StreamPool), through one batched stream and through B single streams.
 """
 import argparse
 import os
@@ -35,8 +37,58 @@ def build_model_pair(name, device, **ov):
     return enc.eval().to(device), dec.eval().to(device)
 
 
+def pool_leg(a, dev, enc, dec):
+    """--pool: B live sessions, one chunk each per tick, three ways in one run (alternating, best of --reps after a
+    warm-up round): (a) StreamPool.push, (b) one StreamingEncoder / StreamingDecoder of batch B (the lower bound: the
+    same kernels without the indirection, but its sessions must start and end together), (c) B separate B = 1 streams
+    pushed one after another (what independent sessions cost without the pool).  One JSON line per (B, frames)."""
+    import json
+
+    from audiotokenization_amd import streaming as S
+
+    model, hop = (dec, 1) if a.decode else (enc, int(enc.hop_length))
+    stream_cls = S.StreamingDecoder if a.decode else S.StreamingEncoder
+    only = a.pool_only.split(",") if a.pool_only else ["pool", "batch", "singles"]
+    for B in a.pool_B:
+        for frames in a.pool_frames:
+            n = frames * hop
+            x = synth_batch(B, a.ticks * frames * int(enc.hop_length), 0, dev)
+            with torch.no_grad():
+                data = dec(enc(x), vq=True)[0] if a.decode else x
+                pool = S.StreamPool(model, B)
+                sids = [pool.open() for _ in range(B)]
+                batch = stream_cls(model)
+                singles = [stream_cls(model) for _ in range(B)]
+                legs = {
+                    "pool": lambda c: pool.push(sids, c),
+                    "batch": lambda c: batch.push(c),
+                    "singles": lambda c: [s.push(c[b:b + 1]) for b, s in enumerate(singles)],
+                }
+                best = {}
+                for rep in range(a.reps + 1):
+                    for name in only:
+                        if name == "setup":  # nothing but the set-up: what a kernel trace of one leg subtracts
+                            continue
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for t in range(a.ticks):
+                            legs[name](data[..., t * n:(t + 1) * n])
+                        torch.cuda.synchronize()
+                        dt = 1e3 * (time.perf_counter() - t0) / a.ticks
+                        if rep:  # the first round warms the weight caches and sizes the state
+                            best[name] = min(best.get(name, dt), dt)
+            print(json.dumps(dict(leg="pool", what="decode" if a.decode else "encode", B=B, frames=frames, ticks=a.ticks,
+                                  ms_per_tick={k: round(v, 3) for k, v in best.items()},
+                                  state_bytes_per_session=pool.state_bytes() // B)), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--pool", action="store_true", help="session-pool push vs one batched stream vs B single streams")
+    p.add_argument("--pool-B", type=int, nargs="+", default=[16, 64])
+    p.add_argument("--pool-frames", type=int, nargs="+", default=[1, 5], help="frames (hops) per session and tick")
+    p.add_argument("--pool-only", default="", help="comma list of pool,batch,singles,setup (a kernel trace of one of them)")
+    p.add_argument("--ticks", type=int, default=10)
     p.add_argument("--B", type=int, default=64)
     p.add_argument("--seconds", type=float, default=10.0)
     p.add_argument("--chunk", type=int, default=12000, help="samples per push (encode) / x hop (decode)")
@@ -51,6 +103,8 @@ def main():
         from audiotokenization_amd import streaming as S
     dev = torch.device("cuda:0")
     enc, dec = build_model_pair("default", device=dev, causal=True)
+    if a.pool:
+        return pool_leg(a, dev, enc, dec)
     n = int(a.seconds * 24000) // 200 * 200
     x = synth_batch(a.B, n, 0, dev)
     with torch.no_grad():
