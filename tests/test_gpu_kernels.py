@@ -289,8 +289,9 @@ def test_aa_activation_ratios(dev, golden):
 @pytest.mark.parametrize("H,layers,B,T", [(64, 2, 3, 50), (512, 1, 2, 20), (128, 2, 70, 9), (1536, 2, 2, 6),
                                           (256, 2, 130, 7), (512, 2, 64, 40), (1536, 1, 64, 25)])
 def test_reslstm(dev, H, layers, B, T, prec):
-    """x6 mode with H in {256, 512, 1024, 1536} runs the persistent kernel (lstm_seq.hip), including
-    batch slicing (B = 130 -> 3 launches per layer); bc_lstm_status must report no timed-out wait."""
+    """x6 and h3 mode with H in {256, 512, 1536} run the persistent kernel (lstm_seq.hip), including batch
+    slicing (B = 130 -> 3 launches per layer); bc_lstm_status must report no timed-out wait.  (H = 1024, every
+    launch-size edge and a metric on the recurrence alone: tests/test_gpu_lstm_matrix.py.)"""
     g = torch.Generator().manual_seed(H + T)
     m = BL.ResLSTM(H, num_layers=layers)
     with torch.no_grad():
