@@ -52,6 +52,7 @@ _SIGS = {
     "bc_lstm_workspace_floats": (L, [I, I, I]),
     "bc_reslstm_fwd": (I, [P, P, I, I, I, I, P, P, P, P, P, P, I, P]),
     "bc_reslstm_fwd_state": (I, [P, P, I, I, I, I, P, P, P, P, P, P, I, P, P, P, P, P]),
+    "bc_reslstm_fwd_state_lens": (I, [P, P, I, I, I, I, P, P, P, P, P, P, I, P, P, P, P, P, P]),
     "bc_reslstm_bidir_workspace_floats": (L, [I, I, I]),
     "bc_reslstm_bidir_fwd": (I, [P, P, I, I, I, I, P, P, P, P, P, P, I, P]),
     "bc_vq_prepare_codebook": (I, [P, P, P, I, I, P]),
@@ -63,6 +64,7 @@ _SIGS = {
     "bc_fsq_codes": (I, [P, I, P, P, P, P, I, I, I, I, P]),
     "bc_stream_window": (I, [P, L, L, P, P, P, P, P, I, I, I, I, P]),
     "bc_stream_window_slots": (I, [P, L, L, P, P, P, P, P, P, I, I, I, I, I, P]),
+    "bc_stream_window_slots_lens": (I, [P, L, L, P, P, P, P, I, P, P, P, I, I, I, I, I, P]),
     "bc_lstm_state_gather": (I, [P, P, P, P, P, I, I, I, I, P]),
     "bc_lstm_state_scatter": (I, [P, P, P, P, P, I, I, I, I, P]),
     "bc_zero_tail": (I, [P, P, P, I, I, L, L, P]),

@@ -383,22 +383,28 @@ class ResLSTM(nn.Module):
         self.lstm = LSTM(dimension, dimension if not bidirectional else dimension // 2, num_layers,
                          batch_first=True, bidirectional=bidirectional)
 
-    def run(self, x, out_snake=None, state=None, return_state: bool = False):
+    def run(self, x, out_snake=None, state=None, return_state: bool = False, lens=None):
         """y = LSTM(x^T)^T + x (then the next Snake when out_snake = (alpha_exp, inv_beta)).  Streaming:
         state = (h0, c0) [num_layers][H][B] device tensors or None (zeros); with return_state the call
-        returns (y, (h_n, c_n)) in the same layout (nn.LSTM's final state, unit-major)."""
+        returns (y, (h_n, c_n)) in the same layout (nn.LSTM's final state, unit-major).  lens: an int32 device
+        tensor (B,) of steps per clip (bc_reslstm_fwd_state_lens): (h_n, c_n) are then each clip's state after its own
+        lens[b] steps, y still holds all T steps; the call returns (y, (h_n, c_n))."""
         x = _as_input(x)
         B, H, T = x.shape
         (wih, whh, bias), _ = self.lstm.prepared(x.device)
         sa, sb = out_snake if out_snake is not None else (None, None)
         if self.lstm.bidirectional:
-            if state is not None or return_state:
+            if state is not None or return_state or lens is not None:
                 raise NotImplementedError("carried state (streaming) needs a unidirectional ResLSTM")
             out = ops.load().reslstm_bidir(x, wih, bias, whh, sa, sb, L.precision_mode())
             L.defer_status(out[1], f"ResLSTM(D={H}, layers={self.lstm.num_layers}, bidirectional, T={T})")
             return out[0]
         h0, c0 = state if state is not None else (None, None)
-        out = ops.load().reslstm(x, wih, bias, whh, sa, sb, L.precision_mode(), h0, c0, return_state)
+        if lens is not None:
+            out = ops.load().reslstm_lens(x, wih, bias, whh, sa, sb, L.precision_mode(), h0, c0, lens)
+            return_state = True
+        else:
+            out = ops.load().reslstm(x, wih, bias, whh, sa, sb, L.precision_mode(), h0, c0, return_state)
         # include/bigcodec.h: out[1] = the call's count of persistent workgroups that timed out; the
         # codec's forward checks it (L.check_status) before its output can be consumed
         L.defer_status(out[1], f"ResLSTM(H={H}, layers={self.lstm.num_layers}, T={T})")

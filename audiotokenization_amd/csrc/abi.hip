@@ -409,7 +409,7 @@ static int reslstm_impl(const float* x, float* out, int B, int H, int T, int num
                         const float* const* w_ih_packed, const float* const* bias,
                         const float* const* w_hh_packed, const float* out_snake_alpha_exp,
                         const float* out_snake_inv_beta, float* workspace, int mode, void* stream,
-                        const float* h0, const float* c0, float* hT, float* cT);
+                        const float* h0, const float* c0, float* hT, float* cT, const int* lens = nullptr);
 
 int bc_reslstm_fwd(const float* x, float* out, int B, int H, int T, int num_layers,
                    const float* const* w_ih_packed, const float* const* bias,
@@ -429,12 +429,26 @@ int bc_reslstm_fwd_state(const float* x, float* out, int B, int H, int T, int nu
                       out_snake_inv_beta, workspace, mode, stream, h0, c0, hT, cT);
 }
 
+int bc_reslstm_fwd_state_lens(const float* x, float* out, int B, int H, int T, int num_layers,
+                              const float* const* w_ih_packed, const float* const* bias,
+                              const float* const* w_hh_packed, const float* out_snake_alpha_exp,
+                              const float* out_snake_inv_beta, float* workspace, int mode, const float* h0,
+                              const float* c0, float* hT, float* cT, const int* lens, void* stream) {
+  if ((h0 == nullptr) != (c0 == nullptr) || (hT == nullptr) != (cT == nullptr)) return BC_ERR_ARG;
+  if (!x || !out || !w_ih_packed || !bias || !w_hh_packed || !workspace || B < 0 || H <= 0 || H % 16 || T < 0 ||
+      num_layers <= 0 || mode < 0 || mode > 3)
+    return BC_ERR_ARG;
+  if (!lstm_use_seq(H, mode)) return BC_ERR_UNSUPPORTED;  // the per-step kernels carry no state: refused before any launch
+  return reslstm_impl(x, out, B, H, T, num_layers, w_ih_packed, bias, w_hh_packed, out_snake_alpha_exp,
+                      out_snake_inv_beta, workspace, mode, stream, h0, c0, hT, cT, lens);
+}
+
 // One direction of one LSTM layer over a ctb sequence: gx = W_ih lin + b (k = 1 conv, Cin input
 // channels), then the recurrence into lout [H][T*B] (the persistent kernel, or one launch per step).
 static int lstm_layer_dir(const float* lin, int Cin, const float* wih, const float* bias, const float* whh,
                           float* lout, float* gx, float* cst, float* const (&frag)[2], int B, int H, int T, int mode,
                           hipStream_t st, const float* h0, const float* c0, float* hT, float* cT, int* call_status,
-                          void* psplit = nullptr) {
+                          void* psplit = nullptr, const int* lens = nullptr) {
   const long long tb = (long long)T * B;
   if (!wih || !whh || !bias) return BC_ERR_ARG;
   ConvArgs a{};
@@ -469,9 +483,9 @@ static int lstm_layer_dir(const float* lin, int Cin, const float* wih, const flo
     LTScope lt(lstm_seq_kernel_name(H, lstm_planes(mode), B < 64 ? B : 64), 2.0 * 4 * H * (double)H * tb,
                4.0 * 5.0 * H * tb, st);
     return lstm_seq_launch(gx, reinterpret_cast<const unsigned short*>(whh), lout, cst, H, T, B, lstm_planes(mode), st,
-                           h0, c0, hT, cT, call_status);
+                           h0, c0, hT, cT, call_status, lens);
   }
-  if (h0 || c0 || hT || cT) return BC_ERR_UNSUPPORTED;  // carried state: the persistent kernel only
+  if (h0 || c0 || hT || cT || lens) return BC_ERR_UNSUPPORTED;  // carried state: the persistent kernel only
   const bool fast = lstm_fast_ok(H);
   for (int t = 0; t < T; ++t) {
     rc = fast ? lstm_step_frag_launch(gx, whh, frag[(t + 1) & 1], frag[t & 1], lout, cst, H, B, T, t, st)
@@ -485,7 +499,7 @@ static int reslstm_impl(const float* x, float* out, int B, int H, int T, int num
                         const float* const* w_ih_packed, const float* const* bias,
                         const float* const* w_hh_packed, const float* out_snake_alpha_exp,
                         const float* out_snake_inv_beta, float* workspace, int mode, void* stream,
-                        const float* h0, const float* c0, float* hT, float* cT) {
+                        const float* h0, const float* c0, float* hT, float* cT, const int* lens) {
   if (!x || !out || !w_ih_packed || !bias || !w_hh_packed || !workspace || B < 0 || H <= 0 ||
       H % 16 || T < 0 || num_layers <= 0 || mode < 0 || mode > 3)
     return BC_ERR_ARG;
@@ -515,7 +529,7 @@ static int reslstm_impl(const float* x, float* out, int B, int H, int T, int num
     const long long so = (long long)l * H * B;  // layer l's [H][B] state
     rc = lstm_layer_dir(lin, H, w_ih_packed[l], bias[l], w_hh_packed[l], lout, gx, cst, frag, B, H, T, mode, st,
                         h0 ? h0 + so : nullptr, c0 ? c0 + so : nullptr, hT ? hT + so : nullptr,
-                        cT ? cT + so : nullptr, call_status, workspace + lstm_ws_head_floats(B, H, T));
+                        cT ? cT + so : nullptr, call_status, workspace + lstm_ws_head_floats(B, H, T), lens);
     if (rc) return rc;
     lin = lout;
     lout = (lout == ya) ? yb : ya;
@@ -639,6 +653,14 @@ int bc_stream_window_slots(const float* x, long long x_batch_stride, long long x
                            int C, int n, int P, int pool_rows, void* stream) {
   return stream_window_slots_launch(x, x_batch_stride, x_row_stride, pool, src, dst, snake_alpha_exp, snake_inv_beta, win,
                                     B, C, n, P, pool_rows, S(stream));
+}
+
+int bc_stream_window_slots_lens(const float* x, long long x_batch_stride, long long x_row_stride, float* pool,
+                                const int* src, const int* dst, const int* lens, int unit, const float* snake_alpha_exp,
+                                const float* snake_inv_beta, float* win, int B, int C, int n, int P, int pool_rows,
+                                void* stream) {
+  return stream_window_slots_lens_launch(x, x_batch_stride, x_row_stride, pool, src, dst, lens, unit, snake_alpha_exp,
+                                         snake_inv_beta, win, B, C, n, P, pool_rows, S(stream));
 }
 
 int bc_lstm_state_gather(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0, int num_layers,

@@ -95,6 +95,9 @@ int stream_window_launch(const float* x, long long xbs, long long xT, const floa
 int stream_window_slots_launch(const float* x, long long xbs, long long xT, float* pool, const int* src, const int* dst,
                                const float* sa, const float* sb, float* win, int B, int C, int n, int P, int pool_rows,
                                hipStream_t st);
+int stream_window_slots_lens_launch(const float* x, long long xbs, long long xT, float* pool, const int* src,
+                                    const int* dst, const int* lens, int unit, const float* sa, const float* sb,
+                                    float* win, int B, int C, int n, int P, int pool_rows, hipStream_t st);
 int lstm_state_gather_launch(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0,
                              int num_layers, int H, int B, int pool_rows, hipStream_t st);
 int lstm_state_scatter_launch(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT,
@@ -124,7 +127,7 @@ long long lstm_seq_workspace_bytes(int H, int T);
 int lstm_seq_launch(const float* gx, const unsigned short* whh, float* y, void* ws, int H, int T, int Btot,
                     int planes, hipStream_t st, const float* h0 = nullptr, const float* c0 = nullptr,
                     float* hT = nullptr, float* cT = nullptr,
-                    int* call_status = nullptr);
+                    int* call_status = nullptr, const int* lens = nullptr);
 int lstm_seq_read_status(int reset);
 int lstm_step_launch(const float* gx, const float* whh_p, float* y, float* cst, int H, int B,
                      int T, int t, hipStream_t st);

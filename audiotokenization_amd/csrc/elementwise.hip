@@ -13,6 +13,8 @@
 //  stream_window    : a causal stream's [carried context | chunk] window (+ Snake) and its next context.
 //  stream_window_slots / lstm_state_gather / lstm_state_scatter : the same step for a pool of independent sessions,
 //                     the carried state indexed by per-entry pool rows (streaming.py StreamPool).
+//  stream_window_slots_lens : stream_window_slots with a chunk length per entry (zeros past it, the context that ends
+//                     there), for a pool push whose sessions deliver different numbers of hops.
 //  zero_tail        : zeros from each clip's own length to the padded end of a ragged batch's rows.
 #include <algorithm>
 #include "bc_common.h"
@@ -287,6 +289,58 @@ int stream_window_slots_launch(const float* x, long long xbs, long long xT, floa
   const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
   hipLaunchKernelGGL(stream_window_slots_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, pool, src, dst, sa, sb, win,
                      C, n, P, (int)rows, pool_rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
+// A chunk length per entry (StreamPool.push(..., hops=)): entry b delivers L = clamp(lens[b] * unit, 0, n) columns,
+// left-aligned in its row of x (lens in hops, unit = this stage's columns per hop).  Its window is [context | chunk[:L]]
+// followed by zeros up to P + n, so every later stage's values past the entry's end are functions of zeros, biases and
+// Snake (finite, and no other entry's business: columns are independent downstream); x is never read at or past L
+// (it may hold NaN there); the next context is the last P columns of [context | chunk[:L]], win[L + i], which with
+// L < P reaches back into the old context.  lens[b] * unit == n for every b is stream_window_slots_kernel bit for bit.
+// Same src / dst contract, same grid.
+__global__ void __launch_bounds__(256) stream_window_slots_lens_kernel(
+    const float* __restrict__ x, long long xbs, long long xT, float* pool, const int* __restrict__ src,
+    const int* __restrict__ dst, const int* __restrict__ lens, int unit, const float* __restrict__ sa,
+    const float* __restrict__ sb, float* __restrict__ win, int C, int n, int P, int rows, int pool_rows) {
+  const int W = P + n;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = row / C, c = row - b * C;
+    const int s = src[b], d = dst[b];
+    const long long want = (long long)lens[b] * unit;
+    const int L = want < 0 ? 0 : want > n ? n : (int)want;
+    const float* xr = x + (long long)b * xbs + (long long)c * xT;
+    float* wr = win + (long long)row * W;
+    const float* cr = (s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * P : nullptr;
+    float* nr = (d >= 0 && BC_DOK(d < pool_rows)) ? pool + ((long long)d * C + c) * P : nullptr;
+    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
+      float v = 0.f;
+      if (j < P) {
+        v = cr ? cr[j] : 0.f;
+      } else if (j - P < L) {
+        v = xr[j - P];
+        if (sa) v = snake(v, a_, b_);
+      }
+      wr[j] = v;
+      if (nr && j >= L && j < L + P && BC_DOK(j - L >= 0 && j - L < P)) nr[j - L] = v;
+    }
+  }
+}
+
+int stream_window_slots_lens_launch(const float* x, long long xbs, long long xT, float* pool, const int* src,
+                                    const int* dst, const int* lens, int unit, const float* sa, const float* sb,
+                                    float* win, int B, int C, int n, int P, int pool_rows, hipStream_t st) {
+  if (!x || !pool || !src || !dst || !lens || !win || B < 0 || C < 1 || n < 1 || P < 1 || pool_rows < 1 || unit < 1)
+    return BC_ERR_ARG;
+  if (xT < n || xbs < (long long)(C - 1) * xT + n || (sa == nullptr) != (sb == nullptr)) return BC_ERR_ARG;
+  const long long rows = (long long)B * C, W = (long long)P + n;
+  if (rows > 0x7fffffffLL || W > 0x7fffffffLL || (long long)pool_rows * C > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
+  if (rows == 0) return BC_OK;
+  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
+  hipLaunchKernelGGL(stream_window_slots_lens_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, pool, src, dst, lens,
+                     unit, sa, sb, win, C, n, P, (int)rows, pool_rows);
   BC_CHECK_LAUNCH();
   return BC_OK;
 }

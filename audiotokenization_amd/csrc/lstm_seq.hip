@@ -78,6 +78,9 @@ struct LstmSeqArgs {
   const float* c0;
   float* hT;
   float* cT;
+  // lens [Btot] (lstm_seq2 only; a session pool's push with a chunk length per clip) or nullptr: clip b's hT / cT
+  // are its state after step clamp(lens[b], 1, T) - 1 instead of the last step; y is all T steps either way
+  const int* lens;
 };
 
 constexpr int LS_STAMP_T = 2048;  // steps recorded per stamped workgroup
@@ -356,6 +359,7 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
   constexpr int NH = 16 * NTH;                 // clips per half
   __shared__ floatx4 red[LS_WAVES][4][64];     // per-wave partial gates of one half's 4 tiles
   __shared__ float hs[NH][LS_U + 1];           // one half's h_t gathered per clip
+  __shared__ int tls[2 * NH];                  // a.lens of the launch's clips (read only when a.lens is given)
   __shared__ int bail;
 
   const int g = blockIdx.x;
@@ -393,6 +397,13 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
     if (cbh < a.nb) cst0 = a.c0[unit_row + cbh];
     if (NH + cbh < a.nb) cst1 = a.c0[unit_row + NH + cbh];
   }
+
+  // a.lens: the step count after which a clip's state goes out, clamped to [1, T] and indexed by the clip's place in
+  // the whole batch (b0 + clip).  Kept in LDS, not in registers: the widest instantiations have none to spare, and
+  // the one read per half-step sits behind the cell update, off the publish path.  Written here, first read after
+  // the barriers of step 0.
+  if (a.lens)
+    for (int i = tid; i < 2 * NH; i += 256) tls[i] = i < a.nb ? min(max(a.lens[a.b0 + i], 1), a.T) : a.T;
 
   const long long hhalf = (long long)H * (LS_NB * P / 2 / 2);  // floats of hseq per half-step
   const int nprod = G / LS_WAVES;
@@ -586,7 +597,7 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
         const long long yi = (long long)(g * LS_U + cu) * TB + (long long)t * a.Btot + a.b0 + clip;
         if (BC_DOK(yi < (long long)a.H * TB)) a.y[yi] = hq;
       }
-      if (t + 1 == a.T && ok) {  // carried state out
+      if (ok && t + 1 == (a.lens ? tls[clip] : a.T)) {  // carried state out (a.lens: at the clip's own last step)
         if (a.hT) a.hT[unit_row + clip] = hq;
         if (a.cT) a.cT[unit_row + clip] = c;
       }
@@ -752,7 +763,7 @@ static bool seq_resident(int KS, int planes, bool halves, int G) {
 
 int lstm_seq_launch(const float* gx, const unsigned short* whh, float* y, void* ws, int H, int T, int Btot,
                     int planes, hipStream_t st, const float* h0, const float* c0, float* hT, float* cT,
-                    int* call_status) {
+                    int* call_status, const int* lens) {
   if (planes != 2 && planes != 3) return BC_ERR_ARG;
   if (!lstm_seq_ok(H)) return BC_ERR_UNSUPPORTED;
   const int G = H / LS_U;
@@ -781,12 +792,13 @@ int lstm_seq_launch(const float* gx, const unsigned short* whh, float* y, void* 
   a.c0 = c0;
   a.hT = hT;
   a.cT = cT;
+  a.lens = lens;
   // BC_LSTM_SEQ_HALVES=1: the single-batch kernel (kept for A/B timing), else two interleaved halves
   static const bool halves = [] {
     const char* e = getenv("BC_LSTM_SEQ_HALVES");
     return !(e && atoi(e) == 1);
   }();
-  if (!halves && (h0 || c0 || hT || cT)) return BC_ERR_UNSUPPORTED;  // carried state: lstm_seq2 only
+  if (!halves && (h0 || c0 || hT || cT || lens)) return BC_ERR_UNSUPPORTED;  // carried state: lstm_seq2 only
   static int resident_checked[4][2] = {};  // per (H/128 case, kernel): 1 ok, -1 refused
   const int ks_idx = H == 256 ? 0 : H == 512 ? 1 : H == 1024 ? 2 : 3;
   int& rs = resident_checked[ks_idx][planes == 2 ? 0 : 1];

@@ -243,9 +243,11 @@ std::vector<Tensor> reslstm_bidir(const Tensor& x, at::TensorList w_ih, at::Tens
 }
 
 // ---- ResLSTM: returns [y, status] (+ [hT, cT]); status = the call's int32 timeout count --------------------------
-std::vector<Tensor> reslstm(const Tensor& x, at::TensorList w_ih, at::TensorList bias, at::TensorList w_hh,
-                            const optional<Tensor>& sa, const optional<Tensor>& sb, int64_t mode,
-                            const optional<Tensor>& h0, const optional<Tensor>& c0, bool return_state) {
+// (lens: reslstm_lens' step count per clip, or nullptr)
+std::vector<Tensor> reslstm_core(const Tensor& x, at::TensorList w_ih, at::TensorList bias, at::TensorList w_hh,
+                                 const optional<Tensor>& sa, const optional<Tensor>& sb, int64_t mode,
+                                 const optional<Tensor>& h0, const optional<Tensor>& c0, bool return_state,
+                                 const Tensor* lens) {
   dev(x, "x");
   TORCH_CHECK_VALUE(x.dim() == 3, "bigcodec::reslstm: x must be (B, H, T)");
   const int64_t L = (int64_t)w_ih.size();
@@ -270,6 +272,16 @@ std::vector<Tensor> reslstm(const Tensor& x, at::TensorList w_ih, at::TensorList
     hT = at::empty({L, H, B}, x.options());
     cT = at::empty({L, H, B}, x.options());
     if (h0.has_value()) TORCH_CHECK_VALUE(h0->sizes() == hT.sizes() && c0->sizes() == cT.sizes(), "bigcodec::reslstm: h0 / c0 must be (layers, H, B)");
+    if (lens) {
+      dev(*lens, "lens", at::kInt);
+      same_device(x, *lens, "lens");
+      TORCH_CHECK_VALUE(lens->dim() == 1 && lens->size(0) == B, "bigcodec::reslstm_lens: lens must be (", B, ",) int32, steps per clip");
+      ok(bc_reslstm_fwd_state_lens(x.data_ptr<float>(), y.data_ptr<float>(), B, H, T, (int)L, pih.data(), pb.data(),
+                                   phh.data(), optf(x, sa, "out_alpha_exp"), optf(x, sb, "out_inv_beta"),
+                                   ws.data_ptr<float>(), i32(mode, "mode"), optf(x, h0, "h0"), optf(x, c0, "c0"),
+                                   hT.data_ptr<float>(), cT.data_ptr<float>(), lens->data_ptr<int>(), stream_of(x)),
+         "bc_reslstm_fwd_state_lens");
+    } else
     ok(bc_reslstm_fwd_state(x.data_ptr<float>(), y.data_ptr<float>(), B, H, T, (int)L, pih.data(), pb.data(), phh.data(),
                             optf(x, sa, "out_alpha_exp"), optf(x, sb, "out_inv_beta"), ws.data_ptr<float>(),
                             i32(mode, "mode"), optf(x, h0, "h0"), optf(x, c0, "c0"), hT.data_ptr<float>(),
@@ -286,6 +298,19 @@ std::vector<Tensor> reslstm(const Tensor& x, at::TensorList w_ih, at::TensorList
   Tensor status = ws.narrow(0, 0, 1).view(at::kInt).clone();
   if (state) return {y, status, hT, cT};
   return {y, status};
+}
+
+std::vector<Tensor> reslstm(const Tensor& x, at::TensorList w_ih, at::TensorList bias, at::TensorList w_hh,
+                            const optional<Tensor>& sa, const optional<Tensor>& sb, int64_t mode,
+                            const optional<Tensor>& h0, const optional<Tensor>& c0, bool return_state) {
+  return reslstm_core(x, w_ih, bias, w_hh, sa, sb, mode, h0, c0, return_state, nullptr);
+}
+
+// ---- reslstm_lens: [y, status, hT, cT] with (hT, cT) the state after each clip's own lens[b] steps -------------------
+std::vector<Tensor> reslstm_lens(const Tensor& x, at::TensorList w_ih, at::TensorList bias, at::TensorList w_hh,
+                                 const optional<Tensor>& sa, const optional<Tensor>& sb, int64_t mode,
+                                 const optional<Tensor>& h0, const optional<Tensor>& c0, const Tensor& lens) {
+  return reslstm_core(x, w_ih, bias, w_hh, sa, sb, mode, h0, c0, true, &lens);
 }
 
 // ---- quantizers ---------------------------------------------------------------------------------------------
@@ -432,6 +457,35 @@ Tensor stream_window_slots_(const Tensor& x, const Tensor& pool, const Tensor& s
                             win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(P, "P"),
                             i32(pool.size(0), "pool rows"), stream_of(x)),
      "bc_stream_window_slots");
+  return win;
+}
+
+Tensor stream_window_slots_lens_(const Tensor& x, const Tensor& pool, const Tensor& src, const Tensor& dst,
+                                 const Tensor& lens, int64_t unit, const optional<Tensor>& a, const optional<Tensor>& ib,
+                                 int64_t P) {
+  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && x.stride(2) == 1,
+                    "bigcodec::stream_window_slots_lens_: x must be a (B, C, n) float32 tensor with unit time stride");
+  const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
+  TORCH_CHECK_VALUE(P >= 1 && n >= 1 && unit >= 1, "bigcodec::stream_window_slots_lens_: P >= 1, unit >= 1 and a non-empty chunk");
+  check_coeffs(a, ib, C, "stream_window_slots_lens_");
+  dev(pool, "pool");
+  same_device(x, pool, "pool");
+  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && pool.size(2) == P,
+                    "bigcodec::stream_window_slots_lens_: pool must be (rows, C, P)");
+  const int* ps = slots(x, src, B, "stream_window_slots_lens_", "src");
+  const int* pd = slots(x, dst, B, "stream_window_slots_lens_", "dst");
+  dev(lens, "lens", at::kInt);
+  same_device(x, lens, "lens");
+  TORCH_CHECK_VALUE(lens.dim() == 1 && lens.size(0) == B, "bigcodec::stream_window_slots_lens_: lens must be (", B, ",) int32, hops per entry");
+  const int* pl = lens.data_ptr<int>();
+  auto win = at::empty({B, C, P + n}, x.options());
+  if (B == 0) return win;
+  ok(bc_stream_window_slots_lens(x.data_ptr<float>(), B > 1 ? x.stride(0) : C * x.stride(1), C > 1 ? x.stride(1) : n,
+                                 pool.data_ptr<float>(), ps, pd, pl, i32(unit, "unit"), optf(x, a, "alpha_exp"),
+                                 optf(x, ib, "inv_beta"), win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"),
+                                 i32(P, "P"), i32(pool.size(0), "pool rows"), stream_of(x)),
+     "bc_stream_window_slots_lens");
   return win;
 }
 
@@ -660,6 +714,10 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("stream_window(Tensor x, Tensor? ctx, Tensor? alpha_exp, Tensor? inv_beta, int P) -> Tensor[]");
   m.def("stream_window_slots_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor? alpha_exp, Tensor? inv_beta, "
         "int P) -> Tensor");
+  m.def("stream_window_slots_lens_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor lens, int unit, "
+        "Tensor? alpha_exp, Tensor? inv_beta, int P) -> Tensor");
+  m.def("reslstm_lens(Tensor x, Tensor[] w_ih_packed, Tensor[] bias, Tensor[] w_hh_packed, Tensor? out_alpha_exp, "
+        "Tensor? out_inv_beta, int mode, Tensor? h0, Tensor? c0, Tensor lens) -> Tensor[]");
   m.def("lstm_state_gather(Tensor h_pool, Tensor c_pool, Tensor src, int B) -> Tensor[]");
   m.def("lstm_state_scatter_(Tensor(a!) h_pool, Tensor(b!) c_pool, Tensor hT, Tensor cT, Tensor dst) -> ()");
   m.def("zero_tail_(Tensor(a!) y, Tensor(b!)? y2, Tensor lens, int tail_max) -> ()");
@@ -691,6 +749,8 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("fsq_codes", &Guarded<&fsq_codes>::call);
   m.impl("stream_window", &Guarded<&stream_window>::call);
   m.impl("stream_window_slots_", &Guarded<&stream_window_slots_>::call);
+  m.impl("stream_window_slots_lens_", &Guarded<&stream_window_slots_lens_>::call);
+  m.impl("reslstm_lens", &Guarded<&reslstm_lens>::call);
   m.impl("lstm_state_gather", &Guarded<&lstm_state_gather>::call);
   m.impl("lstm_state_scatter_", &Guarded<&lstm_state_scatter_>::call);
   m.impl("zero_tail_", &Guarded<&zero_tail_>::call);

@@ -26,7 +26,8 @@ _ns = None
 # every op the extension defines (tests check the registry against this list)
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
-       "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_")
+       "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_",
+       "stream_window_slots_lens_", "reslstm_lens")
 
 
 def load():
@@ -155,6 +156,16 @@ def _register_fakes():
     def _stream_window_slots(x, pool, src, dst, a, ib, P):
         B, C, n = x.shape
         return _new(x, (B, C, P + n))
+
+    @reg("bigcodec::stream_window_slots_lens_")
+    def _stream_window_slots_lens(x, pool, src, dst, lens, unit, a, ib, P):
+        B, C, n = x.shape
+        return _new(x, (B, C, P + n))
+
+    @reg("bigcodec::reslstm_lens")
+    def _reslstm_lens(x, w_ih, bias, w_hh, sa, sb, mode, h0, c0, lens):
+        B, H, _ = x.shape
+        return [_new(x, x.shape), _new(x, (1,), torch.int32), _new(x, (len(w_ih), H, B)), _new(x, (len(w_ih), H, B))]
 
     @reg("bigcodec::lstm_state_gather")
     def _lstm_state_gather(h_pool, c_pool, src, B):

@@ -30,8 +30,9 @@ outputs of the carried frame's own block on the left and the k - s look-ahead ou
 StreamPool serves many independent sessions, which open, close and skip ticks on their own, with one
 batched push: the same stages on a batch of whichever sessions are live, the carried state in per-stage pools on the
 device and indexed by slot (bc_stream_window_slots, bc_lstm_state_gather / bc_lstm_state_scatter).  Sessions in one
-push share the chunk length: a chunk length per session would need the persistent ResLSTM to hand back its state at
-each clip's own last step.
+push may deliver different numbers of hops (`hops=`): the rows are left-aligned in a padded batch, every
+window zeroes the columns past its entry's own length (bc_stream_window_slots_lens) and the persistent ResLSTM hands
+back its state at each entry's own last step (bc_reslstm_fwd_state_lens).
 """
 from __future__ import annotations
 
@@ -277,20 +278,27 @@ class SlotTable:
     def plan(self, sids):
         return plan_rows([(s, self.pushes[s]) for s in sids])
 
-    def commit(self, sids, samples: int) -> None:
-        for s in sids:
+    def commit(self, sids, samples) -> None:
+        """One more push for every session of `sids`; `samples` is one amount for all of them or one per session."""
+        amounts = [samples] * len(sids) if isinstance(samples, int) else list(samples)
+        if len(amounts) != len(sids):
+            raise ValueError(f"{len(amounts)} sample counts for {len(sids)} sessions")
+        for s, a in zip(sids, amounts):
             self.pushes[s] += 1
-            self.samples[s] += samples
+            self.samples[s] += a
 
 
 class _PoolState:
     """The two places a stream touches its carried state, for a pool: the contexts of a stage live in one
     (2 * capacity, C, P) tensor and the ResLSTM state in two (layers, H, 2 * capacity) tensors, allocated at the
     stage's first push and never zeroed (a fresh session reads zeros through src = -1), and the current push's
-    device index arrays `_src` / `_dst` (int32, one pool row per entry) say which rows it reads and writes."""
+    device index arrays `_src` / `_dst` (int32, one pool row per entry) say which rows it reads and writes.  `_hops`
+    (int32 per entry, None: every entry fills the chunk) is the push's hops per entry out of `_n_hops`: every stage's
+    window and the ResLSTM take it with the stage's own columns per hop."""
 
     _rows = 0
-    _src = _dst = None
+    _src = _dst = _hops = None
+    _n_hops = 0
 
     def _window(self, key, x, P: int, act=None):
         if not P:  # no history, no state: the plain window (a dense copy of a strided view, or the Snake alone)
@@ -299,7 +307,10 @@ class _PoolState:
         pool = self._ctx.get(key)
         if pool is None:
             pool = self._ctx[key] = torch.empty(self._rows, x.shape[1], P, device=x.device, dtype=torch.float32)
-        return ops.load().stream_window_slots_(x, pool, self._src, self._dst, sa, sb, P)
+        if self._hops is None:
+            return ops.load().stream_window_slots_(x, pool, self._src, self._dst, sa, sb, P)
+        return ops.load().stream_window_slots_lens_(x, pool, self._src, self._dst, self._hops,
+                                                    x.shape[-1] // self._n_hops, sa, sb, P)
 
     def _lstm_run(self, m: ResLSTM, h):
         ns = ops.load()
@@ -308,7 +319,10 @@ class _PoolState:
             shape = (m.lstm.num_layers, h.shape[1], self._rows)
             pools = self._lstm[id(m)] = tuple(torch.empty(shape, device=h.device, dtype=torch.float32) for _ in "hc")
         h0, c0 = ns.lstm_state_gather(pools[0], pools[1], self._src, h.shape[0])
-        y, (hT, cT) = m.run(h, state=(h0, c0), return_state=True)
+        lens = self._hops
+        if lens is not None and h.shape[-1] != self._n_hops:  # (no preset: their ResLSTMs run at one step per hop)
+            lens = lens * (h.shape[-1] // self._n_hops)
+        y, (hT, cT) = m.run(h, state=(h0, c0), return_state=True, lens=lens)
         ns.lstm_state_scatter_(pools[0], pools[1], hT, cT, self._dst)
         return y
 
@@ -327,21 +341,31 @@ class StreamPool:
         pool = StreamPool(model, capacity)   # a causal BigCodecEncoder or BigCodecDecoder (StreamingEncoder's refusals)
         sid = pool.open()                    # the lowest free slot; RuntimeError when the pool is full
         y = pool.push(sids, x)               # x (len(sids), 1, n) samples / (len(sids), D, n) frames: row i is sids[i]'s
+        y = pool.push(sids, x, hops=[1, 3])  # a chunk length per session: row i holds hops[i] hops, left-aligned
         wav = pool.tokens(sids, codes)       # decoder pools: codes (len(sids), n, Nq) int64 on the device
         pool.close(sid)                      # the slot is free again; nothing is zeroed
 
     Each session gets exactly what its own B = 1 StreamingEncoder / StreamingDecoder would have produced (bit for bit
     in x6; to fp32 rounding in h3, whose block scales depend on the tiling), whatever else is in the push: sessions
     open, close and sit out ticks independently, the order of `sids` is free, and the chunk length n (a multiple of the
-    hop; one n per call) may differ between calls.  The push runs StreamingEncoder's / StreamingDecoder's own stages on
+    hop) may differ between calls and, with `hops`, between the sessions of one call: hops[i] (an int, 1 <= hops[i] <=
+    n_hops = n / hop samples or n frames) says how many hops of row i are session sids[i]'s; the rest of the row is
+    never read (it may hold anything).  The result has the padded shape: entry i's first hops[i] hops are its output,
+    the rest is exactly zero (one bc_zero_tail), and samples(sid) advances by the session's own amount.  Every window
+    then zeroes the columns past its entry's length and stores the context that ends there
+    (bc_stream_window_slots_lens), and the ResLSTM stores each entry's state at its own last step
+    (bc_reslstm_fwd_state_lens); hops rides in the same staged copy as the row indices.  hops=None launches exactly
+    what it always did.  A model whose first stage carries no history has no window to keep the input's tail out, and
+    `hops` is refused for it (NotImplementedError; no preset is such a model).  The push runs StreamingEncoder's / StreamingDecoder's own stages on
     the batch; only the state access differs: one bc_stream_window_slots launch per stage that carries history, one
     bc_lstm_state_gather and one bc_lstm_state_scatter per ResLSTM, all indexed by one (src, dst) pair of pool rows
     per entry (plan_rows: ping-pong rows, so no launch reads a row it writes).  The pair is built on the host, written
     to pinned memory and copied without a wait; no torch compute kernel runs in a push.
 
     Refused on the host before any launch: an unknown, closed or repeated session id, an empty push, a batch
-    dimension other than len(sids), a chunk that is no multiple of the hop (ValueError); a precision other than the
-    one of the pool's first push (RuntimeError).  When a push raises later than that, launches may have been queued
+    dimension other than len(sids), a chunk that is no multiple of the hop, `hops` of another length than `sids`, with
+    an entry that is no int or lies outside [1, n_hops] (ValueError); a precision other than the one of the pool's first
+    push (RuntimeError).  When a push raises later than that, launches may have been queued
     and the state of ITS sessions is undefined: further pushes for them raise RuntimeError until they are closed."""
 
     def __init__(self, model, capacity: int):
@@ -352,6 +376,7 @@ class StreamPool:
         self.capacity, self.hop = self.table.capacity, self._stream.hop
         conv0 = _conv_of((model.model if self.decoder else model.block)[0])
         self.channels = int(conv0.in_channels)  # of a push's input: 1 (samples) or the latent width
+        self._first_history = conv0.pad_left() > 0  # the first stage's window keeps a ragged input's tail out
         self._started = False
         self._pinned = self._event = None
 
@@ -391,6 +416,23 @@ class StreamPool:
             self._stream._check_mode()
         return sids
 
+    def _n_hops(self, n: int) -> int:
+        return n if self.decoder else n // self.hop
+
+    def _check_hops(self, hops, entries: int, n_hops: int):
+        """`hops` of a push as a list of ints (None: None), or ValueError; nothing is launched before it passes."""
+        if hops is None:
+            return None
+        hops = list(hops)
+        if len(hops) != entries:
+            raise ValueError(f"{len(hops)} hop counts for {entries} sessions: hops[i] belongs to sids[i]")
+        for h in hops:
+            if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= n_hops:
+                raise ValueError(f"hops entry {h!r}: an int from 1 to {n_hops} (the chunk's hops)")
+        if not self._first_history:
+            raise NotImplementedError("a chunk length per session needs a first stage with causal history")
+        return hops
+
     def _start(self) -> None:
         if not self._started:  # the precision the pool's state belongs to is the one of its first push
             self._stream._mode, self._started = _lib.precision_mode(), True
@@ -399,7 +441,7 @@ class StreamPool:
         """`rows` (src then dst) into the device tensor `out`: pinned staging and a copy the host does not wait for
         (the wait on the previous copy's event has nothing left to wait for once that push's status was read)."""
         if self._pinned is None or self._pinned.numel() < len(rows):
-            self._pinned = torch.empty(max(len(rows), 2 * self.capacity), dtype=torch.int32, pin_memory=out.is_cuda)
+            self._pinned = torch.empty(max(len(rows), 4 * self.capacity), dtype=torch.int32, pin_memory=out.is_cuda)
             self._event = torch.cuda.Event() if out.is_cuda else None
         elif self._event is not None:
             self._event.synchronize()
@@ -408,29 +450,47 @@ class StreamPool:
         if self._event is not None:
             self._event.record(torch.cuda.current_stream(out.device))
 
-    def push(self, sids, x) -> torch.Tensor:
+    def push(self, sids, x, hops=None) -> torch.Tensor:
         sids = self._admit(sids, x.shape)
+        n_hops = self._n_hops(x.shape[-1])
+        hops = self._check_hops(hops, len(sids), n_hops)
         src, dst = self.table.plan(sids)
         self._start()
-        s = self._stream
+        s, m = self._stream, len(sids)
         try:
             x = _as_input(x)
-            idx = torch.empty(2 * len(sids), dtype=torch.int32, device=x.device)
-            self._stage(src + dst, idx)
-            s._src, s._dst = idx[:len(sids)], idx[len(sids):]
-            y = s.push(x)
+            if hops is None:
+                idx = torch.empty(2 * m, dtype=torch.int32, device=x.device)
+                self._stage(src + dst, idx)
+                s._src, s._dst = idx[:m], idx[m:]
+                y = s.push(x)
+            else:  # the hops and the output lengths ride in the same staged copy as the rows
+                unit = self.hop if self.decoder else 1  # output columns per hop
+                idx = torch.empty(4 * m, dtype=torch.int32, device=x.device)
+                self._stage(src + dst + hops + [h * unit for h in hops], idx)
+                s._src, s._dst, s._hops, s._n_hops = idx[:m], idx[m:2 * m], idx[2 * m:3 * m], n_hops
+                y = s.push(x)
+                ops.load().zero_tail_(y, None, idx[3 * m:], (n_hops - min(hops)) * unit)
         except BaseException:
             self.table.undefined.update(sids)
             raise
-        self.table.commit(sids, y.shape[-1] if self.decoder else x.shape[-1])
+        finally:
+            s._hops = None
+        if hops is None:
+            self.table.commit(sids, y.shape[-1] if self.decoder else x.shape[-1])
+        else:
+            self.table.commit(sids, [h * self.hop for h in hops])
         return y
 
-    def tokens(self, sids, codes) -> torch.Tensor:
-        """codes (len(sids), n, Nq) int64 on the device -> waveform chunks (len(sids), 1, n * hop)."""
+    def tokens(self, sids, codes, hops=None) -> torch.Tensor:
+        """codes (len(sids), n, Nq) int64 on the device -> waveform chunks (len(sids), 1, n * hop); `hops` as in push
+        (the index frames past an entry's own are never decoded into its output)."""
         if not self.decoder:
             raise TypeError("tokens() needs a pool over a decoder")
-        self._admit(sids, (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape, channels=0)
-        return self.push(sids, self._stream.decoder.tokens_to_latent(codes))
+        shape = (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape
+        sids = self._admit(sids, shape, channels=0)
+        self._check_hops(hops, len(sids), shape[2])
+        return self.push(sids, self._stream.decoder.tokens_to_latent(codes), hops)
 
     def graph(self, B: int, n: int) -> "PoolGraph":
         """One pool push of up to B sessions and chunks of n samples (encoder) / frames (decoder) as a HIP graph."""
@@ -443,7 +503,11 @@ class PoolGraph:
     captured kernels write them in place, so there are no copy-back nodes, eager pushes and replays of the same pool
     mix freely, and ONE graph serves any membership: push(sids, x) takes len(sids) <= B sessions, pads the missing
     entries with src = dst = -1 (they read zeros and store nothing) and zero input, replays, and returns the first
-    len(sids) rows of the static output (overwritten by the next push: copy it to keep it).  check as in StreamGraph."""
+    len(sids) rows of the static output (overwritten by the next push: copy it to keep it).  check as in StreamGraph.
+    push(sids, x, hops=...) is StreamPool.push's chunk length per session: hops is one more static device array (a
+    missing entry stays src = dst = -1), and the launches differ from the equal-length push's (the windows and the
+    ResLSTM take the lengths, one bc_zero_tail follows), so they are a second graph over the same static input and
+    index arrays, captured at the first push that gives hops; pushes with and without hops mix freely."""
 
     def __init__(self, pool: StreamPool, B: int, n: int):
         B, n = int(B), int(n)
@@ -459,44 +523,81 @@ class PoolGraph:
         dev = next(p for p in (s.decoder if pool.decoder else s.encoder).parameters()).device
         self.input = torch.zeros(B, pool.channels, n, device=dev)
         self._dirty = 0  # rows of the static input that hold a session's data
-        self._idx = torch.full((2 * B,), -1, dtype=torch.int32, device=dev)
-        s._src, s._dst = self._idx[:B], self._idx[B:]
-        # one eager push of padding entries allocates every pool and warms the weight caches; it stores no state
-        with torch.no_grad():
-            s.push(self.input)
-        torch.cuda.synchronize()
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), _lib.deferred_status() as ticket:
-            with torch.cuda.graph(self._graph):
-                self.output = s.push(self.input)
-        self._status = ticket.items  # the graph's own status words, rewritten by every replay
+        # static index arrays: src | dst | hops | output lengths, B of each (the last two: the graph with hops only)
+        self._n_hops = pool._n_hops(n)
+        self._unit = pool.hop if pool.decoder else 1  # output columns per hop
+        self._padding = [-1] * (2 * B) + [self._n_hops] * B + [self._n_hops * self._unit] * B
+        self._idx = torch.tensor(self._padding, dtype=torch.int32, device=dev)
+        self._graph, self.output, self._status = self._capture(False)
+        self._ragged = None  # (graph, output, status words) of the push with hops
+        self._last = self._status
 
-    def push(self, sids, x, check: bool = True) -> torch.Tensor:
-        pool = self.pool
-        sids = pool._admit(sids, x.shape, most=self.B)
+    def _capture(self, ragged: bool):
+        """One push of B entries over the static input and index arrays as a graph: (graph, its static output, its
+        status words, rewritten by every replay)."""
+        B, s = self.B, self.pool._stream
+        self._idx.copy_(torch.tensor(self._padding, dtype=torch.int32))  # (a later capture: no session's rows)
+        s._src, s._dst = self._idx[:B], self._idx[B:2 * B]
+        if ragged:
+            s._hops, s._n_hops = self._idx[2 * B:3 * B], self._n_hops
+
+        def push():
+            y = s.push(self.input)
+            if ragged:  # sized for the shortest entry there can be: one hop
+                ops.load().zero_tail_(y, None, self._idx[3 * B:], (self._n_hops - 1) * self._unit)
+            return y
+
+        try:
+            # one eager push of padding entries allocates every pool and warms the weight caches; it stores no state
+            with torch.no_grad():
+                push()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.no_grad(), _lib.deferred_status() as ticket:
+                with torch.cuda.graph(graph):
+                    output = push()
+        finally:
+            s._hops = None
+        return graph, output, ticket.items
+
+    def push(self, sids, x, hops=None, check: bool = True) -> torch.Tensor:
+        pool, B = self.pool, self.B
+        sids = pool._admit(sids, x.shape, most=B)
         if x.shape[2] != self.input.shape[2]:
             raise ValueError(f"this graph was captured for chunks of {self.input.shape[2]}, got {x.shape[2]}")
+        hops = pool._check_hops(hops, len(sids), self._n_hops)
         src, dst = pool.table.plan(sids)
-        m, pad = len(sids), [-1] * (self.B - len(sids))
+        m, pad = len(sids), [-1] * (B - len(sids))
         try:
-            pool._stage(src + pad + dst + pad, self._idx)
+            if hops is None:
+                graph, output, self._last = self._graph, self.output, self._status
+                pool._stage(src + pad + dst + pad, self._idx[:2 * B])
+            else:
+                if self._ragged is None:
+                    self._ragged = self._capture(True)
+                graph, output, self._last = self._ragged
+                pool._stage(src + pad + dst + pad + hops + self._padding[2 * B + m:3 * B]
+                            + [h * self._unit for h in hops] + self._padding[3 * B + m:], self._idx)
             self.input[:m].copy_(_as_input(x))
             if self._dirty > m:
                 self.input[m:self._dirty].zero_()
             self._dirty = m
-            self._graph.replay()
+            graph.replay()
             if check:
                 self.check()
         except BaseException:
             pool.table.undefined.update(sids)
             raise
-        pool.table.commit(sids, self.output.shape[-1] if pool.decoder else x.shape[-1])
-        return self.output[:m]
+        if hops is None:
+            pool.table.commit(sids, output.shape[-1] if pool.decoder else x.shape[-1])
+        else:
+            pool.table.commit(sids, [h * pool.hop for h in hops])
+        return output[:m]
 
     def check(self) -> None:
         """Raise BigCodecLibraryError if the last replay's persistent ResLSTM reported a failure (host wait)."""
-        if self._status:
-            _lib._raise_bad(self._status, torch.cat([t.reshape(-1) for t, _ in self._status]).cpu().tolist())
+        if self._last:
+            _lib._raise_bad(self._last, torch.cat([t.reshape(-1) for t, _ in self._last]).cpu().tolist())
 
 
 class StreamGraph:

@@ -201,6 +201,18 @@ int bc_reslstm_fwd_state(const float* x, float* out, int B, int H, int T, int nu
                          const float* const* w_hh_packed, const float* out_snake_alpha_exp,
                          const float* out_snake_inv_beta, float* workspace, int mode, const float* h0,
                          const float* c0, float* hT, float* cT, void* stream);
+/* bc_reslstm_fwd_state_lens: bc_reslstm_fwd_state with a step count per clip (a streaming session pool whose sessions
+ *   deliver chunks of different lengths in one push, streaming.py StreamPool; like streaming itself it stands in for
+ *   no reference behaviour, each session's whole-sequence causal pass defines its result).  lens is a DEVICE array
+ *   int32[B]: hT[l][u][b] / cT[l][u][b] are the state of every layer after step clamp(lens[b], 1, T) - 1 of clip b.
+ *   out is unchanged, all T steps of every clip: the steps past a clip's own length run on and are the caller's to
+ *   ignore.  lens NULL, or every entry == T, is bc_reslstm_fwd_state bit for bit (the same launches; lens only
+ *   selects the step whose state is stored).  Returns 3 before any launch for a shape the per-step kernels serve. */
+int bc_reslstm_fwd_state_lens(const float* x, float* out, int B, int H, int T, int num_layers,
+                              const float* const* w_ih_packed, const float* const* bias,
+                              const float* const* w_hh_packed, const float* out_snake_alpha_exp,
+                              const float* out_snake_inv_beta, float* workspace, int mode, const float* h0,
+                              const float* c0, float* hT, float* cT, const int* lens, void* stream);
 
 /* bc_reslstm_bidir_fwd: ResLSTM(dimension = D, bidirectional=True) (vq/module.py:150-152: nn.LSTM(D, D / 2,
  *   num_layers, batch_first=True, bidirectional=True)), + skip.  x, out: [B][D][T], H = D / 2, D % 32 == 0.
@@ -298,6 +310,17 @@ int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_s
 int bc_stream_window_slots(const float* x, long long x_batch_stride, long long x_row_stride, float* pool, const int* src,
                            const int* dst, const float* snake_alpha_exp, const float* snake_inv_beta, float* win, int B,
                            int C, int n, int P, int pool_rows, void* stream);
+/* bc_stream_window_slots_lens: bc_stream_window_slots with a chunk length per entry.  lens is a DEVICE array int32[B]
+ *   in hops and unit the columns per hop at this stage (n / n_hops of the push): entry b delivers L_b =
+ *   clamp(lens[b] * unit, 0, n) columns, left-aligned in its row of x.  win[b][c][j] is bc_stream_window_slots' value
+ *   for j < P + L_b and 0.0f for P + L_b <= j < P + n; x is never read at or past column L_b (it may hold NaN there);
+ *   the context stored to row dst[b] is win[b][c][L_b + i], i < P: the last P columns of [context | chunk[:L_b]],
+ *   which with L_b < P reach back into the old context.  Every lens[b] * unit == n reproduces bc_stream_window_slots
+ *   bit for bit.  Same src / dst contract and status codes; unit < 1 or a null lens returns 1. */
+int bc_stream_window_slots_lens(const float* x, long long x_batch_stride, long long x_row_stride, float* pool,
+                                const int* src, const int* dst, const int* lens, int unit, const float* snake_alpha_exp,
+                                const float* snake_inv_beta, float* win, int B, int C, int n, int P, int pool_rows,
+                                void* stream);
 int bc_lstm_state_gather(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0, int num_layers,
                          int H, int B, int pool_rows, void* stream);
 int bc_lstm_state_scatter(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT, int num_layers,

@@ -9,6 +9,9 @@ around the whole stream), ms per push and the number of kernel launches per push
 contexts, two-launch ResidualUnits) on the same models for an A/B.  Random weights, synthetic white noise.
 --pool [--decode] [--pool-B 16 64] [--pool-frames 1 5] times a tick of B independent sessions through the session
 pool (StreamPool), through one batched stream and through B single streams.
+--pool --ragged [--decode] [--pool-B 16 64] times a tick in which every session has its own number of hops ready (1 to
+5, drawn per tick with a fixed seed): one push with `hops` against one equal-length push per distinct length
+(DESIGN.md §20).
 """
 import argparse
 import os
@@ -82,12 +85,76 @@ def pool_leg(a, dev, enc, dec):
                                   state_bytes_per_session=pool.state_bytes() // B)), flush=True)
 
 
+def ragged_leg(a, dev, enc, dec):
+    """--pool --ragged: B live sessions, each with 1 ... 5 hops ready per tick (uniform, seeded), two ways in one run
+    (alternating, best of --reps after a warm-up round): (a) one push with `hops` over the batch padded to the tick's
+    longest entry, (b) what a service did before: the sessions grouped by length, one equal-length push per group.
+    Each leg has its own pool of B sessions and walks the same per-session streams; the padded and the grouped
+    batches are assembled before the timed window (both legs get ready-made tensors).  One JSON line per B."""
+    import json
+    import random
+
+    from audiotokenization_amd import streaming as S
+
+    model, unit = (dec, 1) if a.decode else (enc, int(enc.hop_length))
+    for B in a.pool_B:
+        rng = random.Random(a.seed)
+        draws = [[rng.randint(1, 5) for _ in range(B)] for _ in range(a.ticks)]
+        total = max(sum(d[b] for d in draws) for b in range(B))
+        x = synth_batch(B, total * int(enc.hop_length), 0, dev)
+        with torch.no_grad():
+            data = dec(enc(x), vq=True)[0] if a.decode else x
+            pools = {name: S.StreamPool(model, B) for name in ("ragged", "grouped")}
+            sids = {name: [p.open() for _ in range(B)] for name, p in pools.items()}
+            pos, padded, grouped = [0] * B, [], []
+            for hops in draws:
+                n_hops = max(hops)
+                xt = torch.zeros(B, data.shape[1], n_hops * unit, device=dev)
+                for b, h in enumerate(hops):
+                    xt[b, :, :h * unit] = data[b, :, pos[b]:pos[b] + h * unit]
+                padded.append((xt, hops))
+                groups = []
+                for h in sorted(set(hops)):
+                    members = [b for b in range(B) if hops[b] == h]
+                    groups.append((members, torch.stack([data[b, :, pos[b]:pos[b] + h * unit] for b in members])))
+                grouped.append(groups)
+                pos = [p + h * unit for p, h in zip(pos, hops)]
+
+            def run_ragged():
+                pool, ids = pools["ragged"], sids["ragged"]
+                for xt, hops in padded:
+                    pool.push(ids, xt, hops=hops)
+
+            def run_grouped():
+                pool, ids = pools["grouped"], sids["grouped"]
+                for groups in grouped:
+                    for members, xg in groups:
+                        pool.push([ids[b] for b in members], xg)
+
+            best = {}
+            for rep in range(a.reps + 1):
+                for name, leg in (("ragged", run_ragged), ("grouped", run_grouped)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    leg()
+                    torch.cuda.synchronize()
+                    dt = 1e3 * (time.perf_counter() - t0) / a.ticks
+                    if rep:  # the first round warms the weight caches and sizes the state
+                        best[name] = min(best.get(name, dt), dt)
+        print(json.dumps(dict(leg="ragged", what="decode" if a.decode else "encode", B=B, ticks=a.ticks, seed=a.seed,
+                              pushes_per_tick=dict(ragged=1.0, grouped=round(sum(len(g) for g in grouped) / a.ticks, 2)),
+                              ms_per_tick={k: round(v, 3) for k, v in best.items()},
+                              grouped_over_ragged=round(best["grouped"] / best["ragged"], 2))), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--pool", action="store_true", help="session-pool push vs one batched stream vs B single streams")
     p.add_argument("--pool-B", type=int, nargs="+", default=[16, 64])
     p.add_argument("--pool-frames", type=int, nargs="+", default=[1, 5], help="frames (hops) per session and tick")
     p.add_argument("--pool-only", default="", help="comma list of pool,batch,singles,setup (a kernel trace of one of them)")
+    p.add_argument("--ragged", action="store_true", help="with --pool: one push with hops vs one push per distinct length")
+    p.add_argument("--seed", type=int, default=0, help="--ragged: seed of the hops drawn per session and tick")
     p.add_argument("--ticks", type=int, default=10)
     p.add_argument("--B", type=int, default=64)
     p.add_argument("--seconds", type=float, default=10.0)
@@ -104,7 +171,7 @@ def main():
     dev = torch.device("cuda:0")
     enc, dec = build_model_pair("default", device=dev, causal=True)
     if a.pool:
-        return pool_leg(a, dev, enc, dec)
+        return (ragged_leg if a.ragged else pool_leg)(a, dev, enc, dec)
     n = int(a.seconds * 24000) // 200 * 200
     x = synth_batch(a.B, n, 0, dev)
     with torch.no_grad():
