@@ -79,6 +79,8 @@ _SIGS = {
     "bc_logmel_workspace_doubles": (L, [I, L, I]),
     "bc_logmel_l1": (I, [P, P, P, P, P, P, P, I, L, I, I, C.c_float, P]),
     "bc_code_hist": (I, [P, I, P, P, I, L, I, P]),
+    "bc_stoi_workspace_bytes": (L, [I, L, I, I]),
+    "bc_stoi": (I, [P, P, P, P, I, I, I, P, P, P, P, I, L, P]),
     "bc_flac_info": (I, [P, L, P, P, P, P]),
     "bc_flac_decode": (L, [P, L, P, I, L, I]),
     "bc_conv1d_kernel_name": (I, [I, I, I, I, C.c_char_p, I]),

@@ -761,6 +761,20 @@ int bc_code_hist(const void* codes, int code_bits, const int* lens, long long* c
   return code_hist_launch(codes, code_bits, lens, counts, B, T, n_codes, S(stream));
 }
 
+long long bc_stoi_workspace_bytes(int B, long long T, int up, int down) { return stoi_workspace_bytes(B, T, up, down); }
+
+int bc_stoi(const float* clean, const float* proc, const int* lens, const float* filt, int up, int down, int half_len,
+            const float* basis, float* out, int* kept, void* workspace, int B, long long T, void* stream) {
+  if (!clean || !proc || !basis || !out || !kept || !workspace || B <= 0 || T <= 0 || up <= 0 || down <= 0)
+    return BC_ERR_ARG;
+  // one record for the call's five launches.  Both signals at 10 kHz: the resampling taps, then (re, im) of 224 bins x
+  // 256 samples per frame of 128 new samples
+  const double n10 = 2.0 * B * (double)T * up / down;
+  LTScope lt("stoi_kernels", n10 * (2.0 * (2 * half_len + 1) / up + 2.0 * 2.0 * 224.0 * 256.0 / 128.0),
+             8.0 * B * (double)T + 8.0 * n10, S(stream));
+  return stoi_launch(clean, proc, lens, filt, up, down, half_len, basis, out, kept, workspace, B, T, S(stream));
+}
+
 }  // extern "C"
 
 // Diagnostics only (not part of include/bigcodec.h): run the unidirectional ResLSTM's input projection on the
@@ -793,6 +807,7 @@ int bc_dbg_fetch_pw_presplit(unsigned*);
 int bc_dbg_fetch_lstm_seq(unsigned*);
 int bc_dbg_fetch_elementwise(unsigned*);
 int bc_dbg_fetch_metrics(unsigned*);
+int bc_dbg_fetch_stoi(unsigned*);
 int bc_debug_status(unsigned* out) {
   if (!out) return BC_ERR_ARG;
   if (hipDeviceSynchronize() != hipSuccess) return BC_ERR_LAUNCH;
@@ -801,6 +816,7 @@ int bc_debug_status(unsigned* out) {
                                      bc_dbg_fetch_conv1d_x6_p3, bc_dbg_fetch_resunit_x6, bc_dbg_fetch_resunit_w16,
                                      bc_dbg_fetch_resunit_rr,
                                      bc_dbg_fetch_pw_presplit, bc_dbg_fetch_lstm_seq, bc_dbg_fetch_elementwise, bc_dbg_fetch_metrics,
+                                     bc_dbg_fetch_stoi,
                                      bc_dbg_fetch_abi};
   for (auto f : fetch)
     if (f(out)) return BC_ERR_LAUNCH;

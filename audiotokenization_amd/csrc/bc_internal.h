@@ -174,4 +174,9 @@ int logmel_l1_launch(const float* ref, const float* rec, const int* lens, const 
                      hipStream_t st);
 int code_hist_launch(const void* codes, int code_bits, const int* lens, long long* counts, int B, long long T,
                      int n_codes, hipStream_t st);
+
+// STOI (stoi.hip)
+long long stoi_workspace_bytes(int B, long long T, int up, int down);
+int stoi_launch(const float* clean, const float* proc, const int* lens, const float* filt, int up, int down,
+                int half_len, const float* basis, float* out, int* kept, void* ws, int B, long long T, hipStream_t st);
 }  // namespace bc

@@ -15,6 +15,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <tuple>
 #include <vector>
 
 #include "bigcodec.h"
@@ -652,6 +653,34 @@ Tensor logmel_l1(const Tensor& ref, const Tensor& rec, const optional<Tensor>& l
   return out;
 }
 
+std::tuple<Tensor, Tensor> stoi(const Tensor& clean, const Tensor& proc, const optional<Tensor>& lens,
+                                const optional<Tensor>& filt, const Tensor& basis, int64_t up, int64_t down) {
+  check_pair(clean, proc, "stoi");
+  const int64_t B = clean.size(0), T = clean.size(1);
+  const int* pl = opt_lens(clean, lens, B, "stoi");
+  TORCH_CHECK_VALUE(up >= 1 && down >= 1 && up <= (1 << 20) && down <= (1 << 20), "bigcodec::stoi: up, down >= 1");
+  const bool resample = !(up == 1 && down == 1);
+  TORCH_CHECK_VALUE(!resample || filt.has_value(), "bigcodec::stoi: filt is required unless up = down = 1");
+  int64_t half_len = 0;
+  if (resample) {
+    TORCH_CHECK_VALUE(filt->dim() == 1 && filt->numel() >= 3 && filt->numel() % 2 == 1 && filt->numel() < (1 << 24),
+                      "bigcodec::stoi: filt must be (2 * half_len + 1,)");
+    half_len = filt->numel() / 2;
+  }
+  TORCH_CHECK_VALUE(basis.dim() == 2 && basis.size(0) == 448 && basis.size(1) == 256,
+                    "bigcodec::stoi: basis must be (2 * 224, 256)");
+  const long long nws = bc_stoi_workspace_bytes(i32(B, "B"), T, (int)up, (int)down);
+  TORCH_CHECK_VALUE(nws > 0, "bigcodec::stoi: unsupported rate ratio or batch shape");
+  auto ws = at::empty({(int64_t)nws}, clean.options().dtype(at::kByte));
+  auto out = at::empty({B}, clean.options());
+  auto kept = at::empty({B}, clean.options().dtype(at::kInt));
+  ok(bc_stoi(clean.data_ptr<float>(), proc.data_ptr<float>(), pl, resample ? req(clean, *filt, "filt") : nullptr, (int)up,
+             (int)down, (int)half_len, req(clean, basis, "basis"), out.data_ptr<float>(), kept.data_ptr<int>(),
+             ws.data_ptr(), (int)B, T, stream_of(clean)),
+     "bc_stoi");
+  return {out, kept};
+}
+
 void code_hist_(const Tensor& counts, const Tensor& codes, const optional<Tensor>& lens) {
   dev(counts, "counts", at::kLong);
   TORCH_CHECK_VALUE(counts.dim() == 1 && counts.numel() > 0, "bigcodec::code_hist_: counts must be (codebook_size,) int64");
@@ -726,6 +755,7 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("si_snr(Tensor ref, Tensor rec, Tensor? lens) -> Tensor");
   m.def("logmel_l1(Tensor ref, Tensor rec, Tensor? lens, Tensor basis, Tensor mel, int n_fft, float clamp_eps) -> Tensor");
   m.def("code_hist_(Tensor(a!) counts, Tensor codes, Tensor? lens) -> ()");
+  m.def("stoi(Tensor clean, Tensor proc, Tensor? lens, Tensor? filt, Tensor basis, int up, int down) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
@@ -759,4 +789,5 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("si_snr", &Guarded<&si_snr>::call);
   m.impl("logmel_l1", &Guarded<&logmel_l1>::call);
   m.impl("code_hist_", &Guarded<&code_hist_>::call);
+  m.impl("stoi", &Guarded<&stoi>::call);
 }

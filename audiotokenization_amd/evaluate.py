@@ -1,8 +1,8 @@
 """Round-trip evaluation: encode -> VQ -> decode a set of clips in ragged batches and report the quality metrics of
-metrics.RoundTripMetrics (inference_full.py:700-737's validation loop without the host copies; STOI and PESQ are
-not computed).
+metrics.RoundTripMetrics (inference_full.py:700-737's validation loop without the host copies; STOI with --stoi,
+DESIGN.md §21; PESQ is not computed).
 
-    python -m audiotokenization_amd.evaluate --save_path RUN --subsets test-clean --json OUT.json
+    python -m audiotokenization_amd.evaluate --save_path RUN --subsets test-clean --stoi --json OUT.json
 """
 from __future__ import annotations
 
@@ -52,13 +52,16 @@ def _load(item, sample_rate, duration, device) -> torch.Tensor:
 
 def evaluate_round_trip(model, clips_or_paths, batch: int = 16, sample_rate: Optional[int] = None,
                         duration: Optional[float] = None, device=None, per_file: bool = False,
-                        metrics: Optional[RoundTripMetrics] = None) -> dict:
+                        metrics: Optional[RoundTripMetrics] = None, stoi: bool = False,
+                        stoi_clean: str = "ref") -> dict:
     """Round-trip every clip through `model` (a CodecLightningModule or an extract.BigCodecModel) and return
     RoundTripMetrics.compute()'s dict; per_file adds "files": one {"index", "path", "samples", "si_snr",
     "mel_distance"} row per clip (a host copy per batch).  Clips are grouped by length (extract.plan_batches) into
     ragged batches of at most `batch`, both signals are cut to each clip's own length (the shorter of the clip and
     its reconstruction), and a model that refuses ragged batches runs clip by clip.  sample_rate: the rate files are
-    resampled to and the mel scale's (default 16000)."""
+    resampled to and the mel scale's (default 16000).  stoi adds "stoi" and "stoi_short_clips" (and "stoi" to the
+    rows); stoi_clean: "ref" scores the reconstruction against the input, "rec" swaps them as inference_full.py:724
+    does (both ignored when `metrics` is given: that object's own settings hold)."""
     if batch < 1:
         raise ValueError("batch must be >= 1")
     m = _as_model(model)
@@ -67,7 +70,7 @@ def evaluate_round_trip(model, clips_or_paths, batch: int = 16, sample_rate: Opt
     device = torch.device(device) if device is not None else next(enc.parameters()).device
     rate = int(sample_rate) if sample_rate else 16000
     if metrics is None:
-        metrics = RoundTripMetrics(rate, m.codebook_size)
+        metrics = RoundTripMetrics(rate, m.codebook_size, stoi=stoi, stoi_clean=stoi_clean)
     if not _ragged_ok(lm):
         batch = 1
     items = list(clips_or_paths)
@@ -96,10 +99,13 @@ def evaluate_round_trip(model, clips_or_paths, batch: int = 16, sample_rate: Opt
             if per_file:
                 pc = metrics.per_clip()
                 snr, mel = pc["si_snr"].cpu().tolist(), pc["mel_distance"].cpu().tolist()
+                sto = pc["stoi"].cpu().tolist() if "stoi" in pc else None
                 for b, j in enumerate(group):
                     it = items[w0 + j]
                     rows.append({"index": w0 + j, "path": os.fspath(it) if isinstance(it, (str, os.PathLike)) else None,
                                  "samples": own[b], "si_snr": snr[b], "mel_distance": mel[b]})
+                    if sto is not None:
+                        rows[-1]["stoi"] = sto[b]
     result = metrics.compute()
     if per_file:
         result["files"] = sorted(rows, key=lambda r: r["index"])
@@ -107,8 +113,8 @@ def evaluate_round_trip(model, clips_or_paths, batch: int = 16, sample_rate: Opt
 
 
 def main(argv=None):
-    """python -m audiotokenization_amd.evaluate: extract.py's dataset arguments, --batch (default 16), --per_file and
-    --json OUT (the result dict; printed when absent)."""
+    """python -m audiotokenization_amd.evaluate: extract.py's dataset arguments, --batch (default 16), --per_file,
+    --stoi [--stoi_clean ref|rec] and --json OUT (the result dict; printed when absent)."""
     import argparse
 
     p = argparse.ArgumentParser(description="BigCodec round-trip quality metrics on MI355X (inference_full.py)")
@@ -121,6 +127,10 @@ def main(argv=None):
     p.add_argument("--subsets", type=str, nargs="+", required=True)
     p.add_argument("--batch", type=int, default=16, help="clips per ragged round trip")
     p.add_argument("--per_file", action="store_true", help="one row per file under \"files\"")
+    p.add_argument("--stoi", action="store_true", help="also STOI (\"stoi\", \"stoi_short_clips\")")
+    p.add_argument("--stoi_clean", type=str, default="ref", choices=("ref", "rec"),
+                   help="STOI's clean signal: the input (ref, the standard order) or the reconstruction (rec, "
+                        "inference_full.py:724)")
     p.add_argument("--json", type=str, default=None, help="write the result here")
     a = p.parse_args(argv)
     if a.batch < 1:
@@ -137,13 +147,14 @@ def main(argv=None):
         return 1
     paths = [item_path(subset_path, fileid, a.ext_audio) for _, subset_path, fileid in items]
     result = evaluate_round_trip(lm, paths, batch=a.batch, sample_rate=a.sample_rate, duration=a.duration,
-                                 device=device, per_file=a.per_file)
+                                 device=device, per_file=a.per_file, stoi=a.stoi, stoi_clean=a.stoi_clean)
     text = json.dumps(result, indent=1)
     if a.json:
         with open(a.json, "w") as fh:
             fh.write(text + "\n")
+    extra = f", stoi {result['stoi']:.4f}" if a.stoi else ""
     print(text if not a.json else f"{result['clips']} clips: si_snr {result['si_snr']:.3f} dB, mel_distance "
-          f"{result['mel_distance']:.4f}, norm_perplexity {result['norm_perplexity']:.4f} -> {a.json}")
+          f"{result['mel_distance']:.4f}, norm_perplexity {result['norm_perplexity']:.4f}{extra} -> {a.json}")
     return 0
 
 

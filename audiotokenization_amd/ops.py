@@ -27,7 +27,7 @@ _ns = None
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
        "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_",
-       "stream_window_slots_lens_", "reslstm_lens")
+       "stream_window_slots_lens_", "reslstm_lens", "stoi")
 
 
 def load():
@@ -199,3 +199,7 @@ def _register_fakes():
     @reg("bigcodec::code_hist_")
     def _code_hist(counts, codes, lens):
         return None
+
+    @reg("bigcodec::stoi")
+    def _stoi(clean, proc, lens, filt, basis, up, down):
+        return _new(clean, (clean.shape[0],)), _new(clean, (clean.shape[0],), torch.int32)

@@ -369,7 +369,7 @@ int bc_synth_clips(float* x, int B, long long T, long long clip0, void* stream);
 
 /* ---- Round-trip quality metrics (added under ABI 18: additive, no existing entry point changes) -----------------
  * What inference_full.py:570-604, 644-647, 723-737 reports of a reconstruction, where the waveforms already are
- * (STOI and PESQ excepted: DESIGN.md section 16).  ref / rec are [B][T] fp32; lens[b] (int32, device; NULL = every
+ * (PESQ excepted: DESIGN.md section 16; STOI: section 21).  ref / rec are [B][T] fp32; lens[b] (int32, device; NULL = every
  * clip fills T) is clip b's own length: samples at or beyond it are never read, and clip b's result is bit for bit
  * what the clip alone gives.
  * bc_si_snr: out[b] = torchmetrics' ScaleInvariantSignalNoiseRatio(preds = rec, target = ref) in dB over clip b:
@@ -393,6 +393,28 @@ int bc_logmel_l1(const float* ref, const float* rec, const int* lens, const floa
                  double* workspace, int B, long long T, int n_fft, int n_mels, float clamp_eps, void* stream);
 int bc_code_hist(const void* codes, int code_bits, const int* lens, long long* counts, int B, long long T, int n_codes,
                  void* stream);
+
+/* ---- STOI (additive under ABI 18) ----------------------------------------------------------
+ * The short-time objective intelligibility measure of Taal et al. 2011 (non-extended, as the pystoi package computes
+ * it; the written definition is tests/stoi_ref.py): both signals to 10 kHz, the frames (256 / 128, Hann) of the
+ * CLEAN signal more than 40 dB below its loudest dropped from both, STFT (n = 512) of the signals rebuilt from the
+ * kept frames, 15 third-octave band magnitudes from 150 Hz, and per 30-frame segment and band the clipped (-15 dB),
+ * centred, normalised correlation; out[b] is their mean.  clean / proc are [B][T] fp32 and lens as above: samples at
+ * or beyond lens[b] are never read, and clip b's result is bit for bit what the clip alone gives.
+ * bc_stoi: up / down = 10000 / sample rate, reduced (16 kHz: 5 / 8; 1 / 1: no resampling, filt may be NULL).
+ *   filt[2 half_len + 1]: the taps of y[n] = sum_m x[m] filt[down n - up m + half_len], n < ceil(lens[b] up / down)
+ *   (scipy.signal.resample_poly's effective filter); basis[2 * 224][256], 16-byte aligned: rows [0, 224) are
+ *   w[n] cos(2 pi (7 + r) n / 512), rows [224, 448) are -w[n] sin(...), w the 256-point Hann window without its zero
+ *   end points (both built on the host: audiotokenization_amd/metrics.py).  kept[b] (int32): the frames kept; the
+ *   signal rebuilt from them has kept[b] - 1 STFT frames.  out[b] = 1e-5 with fewer than 30 STFT frames, NaN for
+ *   lens[b] <= 0.  workspace: bc_stoi_workspace_bytes(B, T, up, down) bytes (-1: bad or unsupported arguments),
+ *   16-byte aligned: the 10 kHz samples, the frame energies, the kept list and the [2][B][15][frames] band
+ *   magnitudes; no spectrogram is written to memory.  Returns 1 for a null pointer or a non-positive size, 3 for
+ *   up or down above 64 or not reduced, more than 4096 taps, B > 65535 or B T > 2^36, before anything is launched.
+ *   Native fp32 MFMA operands for the DFT; the resampling sums, the frame energies and the correlations are fp64. */
+long long bc_stoi_workspace_bytes(int B, long long T, int up, int down);
+int bc_stoi(const float* clean, const float* proc, const int* lens, const float* filt, int up, int down, int half_len,
+            const float* basis, float* out, int* kept, void* workspace, int B, long long T, void* stream);
 
 /* ---- Bounds-checked debug build (no reference counterpart: SURVEY.md §5 row 2) ------------------------------
  * libbigcodec_hip.so built with -DBC_DEBUG (build_lib.build(debug=True) -> audiotokenization_amd/_debug/, loaded by

@@ -10,6 +10,9 @@ times with device events around the whole arm, between two synchronisations:
   torch        the same quantities composed from torch-ROCm operators: torch.stft + matmul + reductions (float32; the
                spectrograms go through HBM), SI-SNR with float64 accumulation, torch.bincount
 
+  metrics_stoi (--stoi) the metrics arm with STOI on (RoundTripMetrics(stoi=True)): its row adds stoi_ms, the median
+               over the metrics arm's, and no torch composition of STOI is written
+
 A last pass of the metrics arm runs under the launch timers and reports each kernel's summed time.  The torch arm's
 peak allocation is reported next to the metrics arm's.  One JSON line per arm; --out also writes them to a file.
 Reads nothing outside the tree; needs a HIP device."""
@@ -30,6 +33,7 @@ def main(argv=None):
     p.add_argument("--seconds", type=float, default=10.0)
     p.add_argument("--rate", type=int, default=24000)
     p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--stoi", action="store_true", help="add the metrics_stoi arm (DESIGN.md §21)")
     p.add_argument("--out", type=str, default=None)
     a = p.parse_args(argv)
 
@@ -99,6 +103,9 @@ def main(argv=None):
         return e0.elapsed_time(e1), (torch.cuda.max_memory_allocated(dev) - base) / 2 ** 20
 
     arms = {"round_trip": round_trip, "metrics": metrics, "torch": torch_composition}
+    if a.stoi:
+        rtm_stoi = M.RoundTripMetrics(a.rate, size, stoi=True)
+        arms["metrics_stoi"] = lambda: rtm_stoi.update(x, state["rec"], codes=state["codes"])
     lines = []
     with torch.no_grad():
         for fn in arms.values():  # warm-up, in order: the metrics arms read the round trip's output
@@ -128,6 +135,18 @@ def main(argv=None):
                 row.update(share_of_round_trip=round(med["metrics"] / med["round_trip"], 4),
                            vs_torch=round(med["torch"] / med["metrics"], 3),
                            kernels_ms={k: round(d["ms_total"], 3) for k, d in sorted(summ.items())}, **agree)
+            if name == "metrics_stoi":
+                res = rtm_stoi.compute()
+                tm = L.KernelTimer()
+                L.set_timer(tm)
+                try:
+                    arms[name]()
+                    row["kernels_ms"] = {k: round(d["ms_total"], 3) for k, d in sorted(tm.summary().items())}
+                finally:
+                    L.set_timer(None)
+                row.update(stoi_ms=round(med["metrics_stoi"] - med["metrics"], 2),
+                           share_of_round_trip=round(med["metrics_stoi"] / med["round_trip"], 4), stoi=res["stoi"],
+                           stoi_short_clips=res["stoi_short_clips"])
             lines.append(json.dumps(row))
             print(lines[-1], flush=True)
     if a.out:
