@@ -63,6 +63,7 @@ _SIGS = {
     "bc_fsq_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "bc_fsq_codes": (I, [P, I, P, P, P, P, I, I, I, I, P]),
     "bc_stream_window": (I, [P, L, L, P, P, P, P, P, I, I, I, I, P]),
+    "bc_stream_window_la": (I, [P, L, L, P, P, P, P, P, I, I, I, I, I, I, P]),
     "bc_stream_window_slots": (I, [P, L, L, P, P, P, P, P, P, I, I, I, I, I, P]),
     "bc_stream_window_slots_lens": (I, [P, L, L, P, P, P, P, I, P, P, P, I, I, I, I, I, P]),
     "bc_lstm_state_gather": (I, [P, P, P, P, P, I, I, I, I, P]),

@@ -648,6 +648,13 @@ int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_s
                               n, P, S(stream));
 }
 
+int bc_stream_window_la(const float* x, long long x_batch_stride, long long x_row_stride, const float* ctx,
+                        const float* snake_alpha_exp, const float* snake_inv_beta, float* win, float* ctx_out, int B,
+                        int C, int n, int Pin, int R, int Pout, void* stream) {
+  return stream_window_la_launch(x, x_batch_stride, x_row_stride, ctx, snake_alpha_exp, snake_inv_beta, win, ctx_out, B,
+                                 C, n, Pin, R, Pout, S(stream));
+}
+
 int bc_stream_window_slots(const float* x, long long x_batch_stride, long long x_row_stride, float* pool, const int* src,
                            const int* dst, const float* snake_alpha_exp, const float* snake_inv_beta, float* win, int B,
                            int C, int n, int P, int pool_rows, void* stream) {

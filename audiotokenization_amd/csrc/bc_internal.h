@@ -92,6 +92,9 @@ int snake_launch(const float* x, const float* sa, const float* sb, float* y, int
                  long long T, hipStream_t st);
 int stream_window_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa, const float* sb,
                          float* win, float* ctx_out, int B, int C, int n, int P, hipStream_t st);
+int stream_window_la_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa,
+                            const float* sb, float* win, float* ctx_out, int B, int C, int n, int Pin, int R, int Pout,
+                            hipStream_t st);
 int stream_window_slots_launch(const float* x, long long xbs, long long xT, float* pool, const int* src, const int* dst,
                                const float* sa, const float* sb, float* win, int B, int C, int n, int P, int pool_rows,
                                hipStream_t st);

@@ -11,6 +11,8 @@
 //  transpose kernels: [B][C][T] <-> [C][T][B] layouts around the ResLSTM (vq/module.py:160-166).
 //  synth_clips      : counter-hash white noise generated in HBM.
 //  stream_window    : a causal stream's [carried context | chunk] window (+ Snake) and its next context.
+//  stream_window_la : the window of a look-ahead stream's lazy stage: carry in and carry out of different lengths, the
+//                     layer's right zero padding at the flush (streaming.py LookaheadEncoder / LookaheadDecoder).
 //  stream_window_slots / lstm_state_gather / lstm_state_scatter : the same step for a pool of independent sessions,
 //                     the carried state indexed by per-entry pool rows (streaming.py StreamPool).
 //  stream_window_slots_lens : stream_window_slots with a chunk length per entry (zeros past it, the context that ends
@@ -236,6 +238,62 @@ int stream_window_launch(const float* x, long long xbs, long long xT, const floa
   const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
   hipLaunchKernelGGL(stream_window_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, ctx, sa, sb, win, ctx_out, C, n,
                      P, (int)rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
+// Look-ahead streaming (streaming.py LookaheadEncoder / LookaheadDecoder): a stage of a non-causal
+// model is a lazy valid conv that carries the input columns it has not finished with, so its carry grows during the
+// first pushes (Pout > Pin), may reach back into the old carry when a chunk is short (Pout > n), and at the flush the
+// layer's own right zero padding follows the last sample.  For each (b, c) row, with S = Pin + n:
+//   win[j]     = j < Pin ? ctx[j] : j < S ? act(x[j - Pin]) : 0.0f      (j < S + R)
+//   ctx_out[i] = win[S - Pout + i]                                       (i < Pout <= S: never a right zero)
+// Same snake(), same missing-ctx zeros, same strided x and same 2-D grid as stream_window_kernel, whose values it
+// reproduces bit for bit with Pin == Pout, R == 0.  n == 0 (a flush without new input) never dereferences x.
+// Accesses are one float per lane, coalesced along the row: the three streams of a row start at row * (S + R),
+// row * Pin and a strided view's column offset (3d behind a one-launch ResidualUnit), with Pin = 6d = 6, 18, 54 in
+// steady state, so they are never 16-byte aligned together and a vector path would not be taken by any stage.
+__global__ void __launch_bounds__(256) stream_window_la_kernel(const float* __restrict__ x, long long xbs, long long xT,
+                                                               const float* __restrict__ ctx, const float* __restrict__ sa,
+                                                               const float* __restrict__ sb, float* __restrict__ win,
+                                                               float* __restrict__ ctx_out, int C, int n, int Pin, int R,
+                                                               int Pout, int rows) {
+  const int S = Pin + n, W = S + R, keep = S - Pout;
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = row / C, c = row - b * C;
+    const float* xr = x + (long long)b * xbs + (long long)c * xT;
+    float* wr = win + (long long)row * W;
+    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
+      float v = 0.f;
+      if (j < Pin) {
+        if (ctx && BC_DOK(j >= 0 && row < rows)) v = ctx[(long long)row * Pin + j];
+      } else if (j < S) {
+        if (BC_DOK(j - Pin >= 0 && j - Pin < n && j - Pin < xT)) {
+          v = xr[j - Pin];
+          if (sa) v = snake(v, a_, b_);
+        }
+      }
+      if (BC_DOK(j >= 0 && j < W && row < rows)) wr[j] = v;
+      if (j >= keep && j < S && BC_DOK(ctx_out != nullptr && j - keep >= 0 && j - keep < Pout))
+        ctx_out[(long long)row * Pout + (j - keep)] = v;
+    }
+  }
+}
+
+int stream_window_la_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa,
+                            const float* sb, float* win, float* ctx_out, int B, int C, int n, int Pin, int R, int Pout,
+                            hipStream_t st) {
+  if (!win || B < 0 || C < 1 || n < 0 || Pin < 0 || R < 0 || Pout < 0) return BC_ERR_ARG;
+  if (n > 0 && (!x || xT < n || xbs < (long long)(C - 1) * xT + n)) return BC_ERR_ARG;
+  if ((sa == nullptr) != (sb == nullptr) || (ctx_out == nullptr) != (Pout == 0)) return BC_ERR_ARG;
+  const long long rows = (long long)B * C, S = (long long)Pin + n, W = S + R;
+  if (W < 1 || Pout > S) return BC_ERR_ARG;
+  if (rows > 0x7fffffffLL || W > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
+  if (rows == 0) return BC_OK;
+  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
+  hipLaunchKernelGGL(stream_window_la_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, ctx, sa, sb, win, ctx_out, C, n,
+                     Pin, R, Pout, (int)rows);
   BC_CHECK_LAUNCH();
   return BC_OK;
 }

@@ -429,6 +429,30 @@ std::vector<Tensor> stream_window(const Tensor& x, const optional<Tensor>& ctx, 
   return {win, nctx};
 }
 
+// ---- stream_window_la: the window of a look-ahead stream's lazy stage (carry in / carry out of different lengths,
+// right zeros at the flush); an empty x (n == 0) is a flush without new input -------------------------------------
+std::vector<Tensor> stream_window_la(const Tensor& x, const optional<Tensor>& ctx, const optional<Tensor>& a,
+                                     const optional<Tensor>& ib, int64_t Pin, int64_t R, int64_t Pout) {
+  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && (x.size(2) == 0 || x.stride(2) == 1),
+                    "bigcodec::stream_window_la: x must be a (B, C, n) float32 tensor with unit time stride");
+  const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
+  TORCH_CHECK_VALUE(Pin >= 0 && R >= 0 && Pout >= 0 && Pin + n + R >= 1 && Pout <= Pin + n,
+                    "bigcodec::stream_window_la: Pin, R, Pout >= 0, a non-empty window and Pout <= Pin + n");
+  check_coeffs(a, ib, C, "stream_window_la");
+  if (ctx)
+    TORCH_CHECK_VALUE(ctx->sizes() == at::IntArrayRef({B, C, Pin}), "bigcodec::stream_window_la: ctx must be (B, C, Pin)");
+  auto win = at::empty({B, C, Pin + n + R}, x.options());
+  auto nctx = at::empty({B, C, Pout}, x.options());
+  const int64_t xT = n && C > 1 ? x.stride(1) : n, xbs = n && B > 1 ? x.stride(0) : C * xT;  // (size-1 dims: any stride)
+  ok(bc_stream_window_la(n ? x.data_ptr<float>() : nullptr, xbs, xT, optf(x, ctx, "ctx"), optf(x, a, "alpha_exp"),
+                         optf(x, ib, "inv_beta"), win.data_ptr<float>(), Pout ? nctx.data_ptr<float>() : nullptr,
+                         i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(Pin, "Pin"), i32(R, "R"), i32(Pout, "Pout"),
+                         stream_of(x)),
+     "bc_stream_window_la");
+  return {win, nctx};
+}
+
 // ---- the streaming session pool: stream_window over pool rows, and the ResLSTM state gather / scatter ----------
 const int* slots(const Tensor& ref, const Tensor& t, int64_t B, const char* op, const char* name) {
   dev(t, name, at::kInt);
@@ -741,6 +765,7 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("fsq(Tensor z, Tensor w_in, Tensor b_in, Tensor w_out, Tensor b_out, Tensor consts) -> Tensor[]");
   m.def("fsq_codes(Tensor idx, Tensor w_out, Tensor b_out, int[] levels) -> Tensor");
   m.def("stream_window(Tensor x, Tensor? ctx, Tensor? alpha_exp, Tensor? inv_beta, int P) -> Tensor[]");
+  m.def("stream_window_la(Tensor x, Tensor? ctx, Tensor? alpha_exp, Tensor? inv_beta, int Pin, int R, int Pout) -> Tensor[]");
   m.def("stream_window_slots_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor? alpha_exp, Tensor? inv_beta, "
         "int P) -> Tensor");
   m.def("stream_window_slots_lens_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor lens, int unit, "
@@ -778,6 +803,7 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("fsq", &Guarded<&fsq>::call);
   m.impl("fsq_codes", &Guarded<&fsq_codes>::call);
   m.impl("stream_window", &Guarded<&stream_window>::call);
+  m.impl("stream_window_la", &Guarded<&stream_window_la>::call);
   m.impl("stream_window_slots_", &Guarded<&stream_window_slots_>::call);
   m.impl("stream_window_slots_lens_", &Guarded<&stream_window_slots_lens_>::call);
   m.impl("reslstm_lens", &Guarded<&reslstm_lens>::call);

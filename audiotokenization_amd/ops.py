@@ -27,7 +27,7 @@ _ns = None
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
        "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_",
-       "stream_window_slots_lens_", "reslstm_lens", "stoi")
+       "stream_window_slots_lens_", "reslstm_lens", "stoi", "stream_window_la")
 
 
 def load():
@@ -151,6 +151,11 @@ def _register_fakes():
     def _stream_window(x, ctx, a, ib, P):
         B, C, n = x.shape
         return [_new(x, (B, C, P + n)), _new(x, (B, C, P))]
+
+    @reg("bigcodec::stream_window_la")
+    def _stream_window_la(x, ctx, a, ib, Pin, R, Pout):
+        B, C, n = x.shape
+        return [_new(x, (B, C, Pin + n + R)), _new(x, (B, C, Pout))]
 
     @reg("bigcodec::stream_window_slots_")
     def _stream_window_slots(x, pool, src, dst, a, ib, P):

@@ -33,6 +33,12 @@ device and indexed by slot (bc_stream_window_slots, bc_lstm_state_gather / bc_ls
 push may deliver different numbers of hops (`hops=`): the rows are left-aligned in a padded batch, every
 window zeroes the columns past its entry's own length (bc_stream_window_slots_lens) and the persistent ResLSTM hands
 back its state at each entry's own last step (bc_reslstm_fwd_state_lens).
+
+LookaheadEncoder / LookaheadDecoder stream the NON-causal models (`default`, `base`) as well: a conv with
+symmetric padding is a causal conv whose output arrives late, so every stage runs as a lazy valid conv over [carry | new]
+(bc_stream_window_la), emits what is final and holds the rest; finish() flushes each layer's own right zero padding.  The
+result equals the whole-sequence forward after a fixed look-ahead (lookahead_samples: 2451 samples for `default`).  The
+classes above keep refusing non-causal models.
 """
 from __future__ import annotations
 
@@ -218,6 +224,376 @@ class StreamingDecoder(StreamingEncoder):
         self.reset()
         outs = [self.push(z[..., i:i + chunk]) for i in range(0, z.shape[-1], chunk)]
         return torch.cat(outs, dim=2)
+
+
+# ---- look-ahead streaming: non-causal models as exact streams with a fixed algorithmic delay ----------
+#
+# The whole-sequence forward defines the result: each layer zero-pads its own input at both of its own ends.  A conv with
+# symmetric padding is a causal conv whose output arrives late, so every stage runs as a LAZY VALID CONV: it holds a
+# carry of the input columns it has not finished with (at the stream's start: its left padding, as zeros), forms
+# [carry | new], emits the outputs whose whole receptive field is there and keeps the rest; the flush appends the layer's
+# own right zero padding and emits what is left.  All of the arithmetic lives in _stage_row; lookahead_plan tabulates
+# it and the classes execute the same rows.
+
+class _Stage:
+    """One lazy stage: kind "conv" (a Conv1dWN behind `act`), "unit" (a ResidualUnit: a k = 7 lazy conv over the raw
+    input), "lstm" (carried state, no geometry) or "convT" (a transposed conv behind `act`).  k, s, d, pl, pr: kernel,
+    stride, dilation and the layer's own left / right zero padding; hist: input frames of history a transposed conv's
+    output block needs."""
+
+    def __init__(self, kind, module, act=None, k=1, s=1, d=1, pl=0, pr=0, hist=0, epilogue=0):
+        self.kind, self.module, self.act, self.epilogue = kind, module, act, epilogue
+        self.k, self.s, self.d, self.pl, self.pr, self.hist = k, s, d, pl, pr, hist
+
+    def start(self):
+        """(carry, seen, emitted) at the stream's start: the left padding as carried zeros."""
+        return (self.pl if self.kind in ("conv", "unit") else 0, 0, 0)
+
+
+def _conv_stage(wrapper, act=None, epilogue=0, kind="conv"):
+    c = _conv_of(wrapper)
+    return _Stage(kind, c, act, c.kernel_size, c.stride, c.dilation, c.pad_left(),
+                  0 if c.causal_pad is not None else c.padding, epilogue=epilogue)
+
+
+def _convT_stage(wrapper, act):
+    conv = wrapper.conv if isinstance(wrapper, CausalConvTranspose1d) else wrapper
+    if conv.kernel_size % conv.stride:
+        raise NotImplementedError(f"streaming transposed conv needs kernel_size % stride == 0 (k={conv.kernel_size}, "
+                                  f"s={conv.stride})")
+    return _Stage("convT", conv, act, conv.kernel_size, conv.stride, 1, conv.padding, 0,
+                  hist=conv.kernel_size // conv.stride - 1)
+
+
+def _unit_stage(ru):
+    st = _conv_stage(ru.block[1], kind="unit")
+    st.module = ru
+    return st
+
+
+def lookahead_stages(model):
+    """The lazy stages of a BigCodecEncoder / BigCodecDecoder in flow order: one per producer of the model's own
+    per-layer length table (frame_lengths / sample_lengths with per_layer=True, rows 1 on).  Refuses what looks ahead
+    without bound: anti-aliased activations and a bidirectional ResLSTM."""
+    if any(getattr(m, "antialias", False) for m in model.modules()):
+        raise NotImplementedError("anti-aliased activations replicate-pad at the clip's end: not streamable")
+    if any(isinstance(m, ResLSTM) and m.lstm.bidirectional for m in model.modules()):
+        raise NotImplementedError("a bidirectional ResLSTM reads the whole clip backwards: not streamable")
+    stages = []
+    if hasattr(model, "tokens_to_latent"):
+        m = list(model.model)
+        stages.append(_conv_stage(m[0]))
+        for st in m[1:-3]:
+            if isinstance(st, ResLSTM):
+                stages.append(_Stage("lstm", st))
+            elif isinstance(st, DecoderBlock):
+                sub = list(st.block)
+                stages.append(_convT_stage(sub[1], sub[0]))
+                stages += [_unit_stage(ru) for ru in sub[2:]]
+            else:
+                raise NotImplementedError(f"unexpected decoder stage {type(st).__name__}")
+        stages.append(_conv_stage(m[-2], m[-3], epilogue=1))  # the decoder's nn.Tanh in the epilogue
+    else:
+        blk = list(model.block)
+        stages.append(_conv_stage(blk[0]))
+        for st in blk[1:-2]:
+            if isinstance(st, EncoderBlock):
+                sub = list(st.block)
+                stages += [_unit_stage(ru) for ru in sub[:-2]]
+                stages.append(_conv_stage(sub[-1], sub[-2]))
+            elif isinstance(st, ResLSTM):
+                stages.append(_Stage("lstm", st))
+            else:
+                raise NotImplementedError(f"unexpected encoder stage {type(st).__name__}")
+        stages.append(_conv_stage(blk[-1], blk[-2]))
+    return stages
+
+
+def _stage_row(st: _Stage, state, new: int, flush: bool):
+    """One push of one stage: ((carry_in, new, right_zeros, outputs, carry_out), next state).  state = (carry, seen,
+    emitted): the carried input columns, and for a transposed conv the frames seen and the outputs emitted so far."""
+    carry, seen, emitted = state
+    if st.kind == "lstm":
+        return (0, new, 0, new, 0), (0, seen + new, emitted + new)
+    if st.kind == "convT":
+        # N frames seen: output o reads frames <= (o + p) // s, so o < N * s - p is final; the flush emits the rest
+        N = seen + new
+        total = st.module.out_len(N) if N > 0 else 0
+        upto = total if flush else min(max(0, N * st.s - st.pl), total)
+        keep = 0 if flush else min(st.hist, carry + new)
+        return (carry, new, 0, upto - emitted, keep), (keep, N, upto)
+    R = st.pr if flush else 0
+    span, have = (st.k - 1) * st.d, carry + new + R
+    out = 0 if have <= span else (have - span - 1) // st.s + 1
+    keep = 0 if flush else have - out * st.s  # the suffix from column out * s on
+    return (carry, new, R, out, keep), (keep, seen + new, emitted + out)
+
+
+def _plan_push(stages, states, n: int, flush: bool):
+    """One push of n input columns through every stage: (rows, next states)."""
+    rows, nxt = [], []
+    for st, state in zip(stages, states):
+        row, state = _stage_row(st, state, n, flush)
+        rows.append(row)
+        nxt.append(state)
+        n = row[3]
+    return rows, nxt
+
+
+def lookahead_plan_stages(stages, chunks, last: int = 0):
+    """lookahead_plan for a list of stages."""
+    states = [st.start() for st in stages]
+    plan = []
+    for i, n in enumerate(list(chunks) + [last]):
+        rows, states = _plan_push(stages, states, int(n), i == len(chunks))
+        plan.append(rows)
+    return plan
+
+
+def lookahead_plan(model, chunks, last: int = 0):
+    """What a look-ahead stream of `model` does with pushes of `chunks` input columns (samples for an encoder, frames
+    for a decoder) and a finish() with `last` more: plan[i][j] = (carry_in, new, right_zeros, outputs, carry_out) of
+    stage j (lookahead_stages order) in push i; the last entry is the flush.  Pure host arithmetic; LookaheadEncoder /
+    LookaheadDecoder execute these rows."""
+    return lookahead_plan_stages(lookahead_stages(model), chunks, last)
+
+
+def lookahead_samples(model) -> int:
+    """The algorithmic look-ahead in samples: how far beyond its own position (a frame's own hop of samples; a sample
+    itself) output 0 reads, summed over the stages at their rates.  A conv reaches (k - 1) d - pad_left - (s - 1)
+    columns to the right of its output's own s input columns, at its input's rate; a transposed conv with padding p
+    reads frames <= (o + p) // s for output o, p columns ahead at its OUTPUT's rate.  An encoder's frame 0 is final once
+    look-ahead + hop samples are in, a decoder's sample 0 once look-ahead // hop + 1 frames are.  0 for a causal model."""
+    stages = lookahead_stages(model)
+    decoder = hasattr(model, "tokens_to_latent")
+    rate, total = (int(model.hop_length) if decoder else 1), 0
+    for st in stages:
+        if st.kind in ("conv", "unit"):
+            total += ((st.k - 1) * st.d - st.pl - (st.s - 1)) * rate
+            rate *= st.s
+        elif st.kind == "convT":
+            rate //= st.s
+            total += st.pl * rate
+    return total
+
+
+class _LookaheadStream:
+    """The stream both look-ahead classes share: the stages, their host-side states and carried tensors, and the
+    execution of one plan row per stage and push."""
+
+    _what = "samples"
+
+    def __init__(self, model):
+        self.model = model
+        self.stages = lookahead_stages(model)
+        self.hop = int(model.hop_length)
+        self.lookahead = lookahead_samples(model)
+        self.reset()
+
+    def reset(self):
+        self._states = [st.start() for st in self.stages]
+        self._carry: Dict[int, torch.Tensor] = {}
+        self._lstm: Dict[int, tuple] = {}
+        self._done = False
+        self._like = None  # (batch size, device) of the stream, from its first input
+        self.samples = 0
+        self.rows = None  # the plan rows of the last push (tests compare them with lookahead_plan's)
+        self._mode = _lib.precision_mode()
+
+    _check_mode = StreamingEncoder._check_mode
+
+    # ---- the stages ----------------------------------------------------------------------------------------------
+    def _window(self, j: int, x, row, act=None, store: bool = True):
+        """[carry | act(x) | right zeros] of stage j for plan row `row`; the last carry_out columns are kept."""
+        cin, _, R, _, cout = row
+        sa, sb = act.act.coeffs(x.device) if act is not None else (None, None)
+        win, nctx = ops.load().stream_window_la(x, self._carry.get(j) if cin else None, sa, sb, cin, R,
+                                                cout if store else 0)
+        if store:
+            self._carry[j] = nctx if cout else None
+        return win
+
+    def _empty(self, x, channels: int):
+        return torch.empty(x.shape[0], channels, 0, device=x.device, dtype=torch.float32)
+
+    def _run_conv(self, j, st, x, row):
+        cin, new, R, out, cout = row
+        c = st.module
+        if not (cin or R or cout) and st.act is None and new and x.is_contiguous():
+            return c.run(x, None, st.epilogue)  # no carry, no padding: the conv itself
+        if not (new or R):  # nothing arrived and nothing to flush: the carry stays as it is
+            return self._empty(x, c.out_channels)
+        win = self._window(j, x, row, st.act)
+        if not out:
+            return self._empty(x, c.out_channels)
+        return c.run(win, None, st.epilogue, pad_left=0)
+
+    def _run_unit(self, j, st, x, row, flush: bool):
+        cin, new, R, out, cout = row
+        ru = st.module
+        if not new and (not flush or not out):
+            return self._empty(x, _conv_of(ru.block[1]).out_channels)
+        cfg = ru._fused_cfg()
+        raw = self._window(j, x, (cin, new, 0, out, cout))  # the raw window never carries the padding: see below
+        if not out:
+            return self._empty(x, raw.shape[1])
+        if cfg >= 0 and ru.snake_on_load():
+            # one launch with the unit's own padding: column c of the window sees columns c - pl ... c + pr, the
+            # residual is the same column; [pl, W - pr) are exact, and at the flush the kernel's own right zero
+            # padding is the layer's, so [pl, W) are
+            y = ru._flow_fused(cfg, raw, None, True, None)[0]
+            return y[:, :, st.pl:st.pl + out]
+        conv7, conv1 = _conv_of(ru.block[1]), _conv_of(ru.block[3])
+        aw = self._window(j, raw, (0, raw.shape[-1], R, out, 0), ru.block[0], store=False)  # snake(0) = 0
+        t = conv7.run(aw, None, 0, ru.block[2].act.coeffs(x.device), pad_left=0)
+        res = self._window(j, raw[:, :, st.pl:st.pl + out], (0, out, 0, out, 0), store=False)
+        return conv1.run(t, res)
+
+    def _run_convT(self, j, st, x, row):
+        cin, new, _, out, cout = row
+        conv = st.module
+        _, seen, emitted = self._states[j]
+        if new:
+            win = self._window(j, x, row, st.act)
+        else:
+            win = self._carry.get(j)
+        if not out:
+            return self._empty(x, conv.out_channels)
+        phases, _, bias, cfg = conv.prepared(win.device, conv.phase_cfg(win.shape[0], win.shape[-1]))
+        # the window's first frame is frame seen - cin of the stream and the first new output is `emitted`: in the
+        # window's own full (unpadded, uncropped) output that is column emitted + p - (seen - cin) s, which the
+        # kernel's crop argument skips; out_len stops before the outputs a later frame still adds to
+        crop = emitted + st.pl - (seen - cin) * st.s
+        return ops.load().conv_transpose1d(win, phases, bias, None, None, conv.out_channels, out, st.k, st.s, crop, cfg,
+                                           False)[0]
+
+    def _run_lstm(self, st, x):
+        if not x.shape[-1]:
+            return x
+        m = st.module
+        if not x.is_contiguous():
+            x = ops.load().stream_window_la(x, None, None, None, 0, 0, 0)[0]
+        y, state = m.run(x, state=self._lstm.get(id(m)), return_state=True)
+        self._lstm[id(m)] = state
+        return y
+
+    def _flow(self, x, flush: bool):
+        rows, states = _plan_push(self.stages, self._states, x.shape[-1], flush)
+        h = x
+        for j, (st, row) in enumerate(zip(self.stages, rows)):
+            if st.kind == "conv":
+                h = self._run_conv(j, st, h, row)
+            elif st.kind == "unit":
+                h = self._run_unit(j, st, h, row, flush)
+            elif st.kind == "convT":
+                h = self._run_convT(j, st, h, row)
+            else:
+                h = self._run_lstm(st, h)
+            if h.shape[-1] != row[3]:
+                raise RuntimeError(f"look-ahead stage {j} ({st.kind}) emitted {h.shape[-1]} columns, its plan row {row}")
+        self._states, self.rows = states, rows
+        _lib.check_status()
+        return h
+
+    def _admit(self, x, flush: bool):
+        if self._done:
+            raise RuntimeError("the stream was finished: reset() it before the next push")
+        self._check_mode()
+        if not isinstance(x, torch.Tensor) or x.dim() != 3 or x.shape[1] != self.stages[0].module.in_channels:
+            raise ValueError(f"a look-ahead stream takes (B, {self.stages[0].module.in_channels}, n) tensors")
+        if not flush and (x.shape[-1] < 1 or (self._what == "samples" and x.shape[-1] % self.hop)):
+            raise ValueError(f"chunk of {x.shape[-1]} {self._what}: must be a positive multiple of the hop "
+                             f"({self.hop if self._what == 'samples' else 1}); finish() takes any length")
+        if x.is_cuda and x.dtype == torch.float32 and (x.stride(2) == 1 or not x.shape[-1]):
+            pass  # a view with unit time stride (a slice of a clip) is read in place by the first window
+        else:
+            x = _as_input(x)
+        if self._like is None:
+            self._like = (x.shape[0], x.device)
+        elif self._like[0] != x.shape[0]:
+            raise ValueError(f"a batch of {x.shape[0]} on a stream of {self._like[0]}: the batch size is fixed per stream")
+        return x
+
+    def _count(self, n_in: int, n_out: int):
+        self.samples += n_in
+
+    def push(self, x) -> torch.Tensor:
+        x = self._admit(x, False)
+        with _lib.status_scope():
+            y = self._flow(x, False)
+        self._count(x.shape[-1], y.shape[-1])
+        return y
+
+    def finish(self, x=None) -> torch.Tensor:
+        """Flush: an optional last chunk of any length, then every layer's own right zero padding; returns the frames
+        (samples) that were still held back.  `x=None` needs at least one earlier push (its batch size and device)."""
+        if x is None:
+            if self._like is None:
+                raise ValueError("finish() without input on a stream that saw none: nothing to flush")
+            x = torch.empty(self._like[0], self.stages[0].module.in_channels, 0, device=self._like[1],
+                            dtype=torch.float32)
+        x = self._admit(x, True)
+        with _lib.status_scope():
+            y = self._flow(x, True)
+        self._count(x.shape[-1], y.shape[-1])
+        self._done = True
+        return y
+
+    def _chunked(self, x, chunk: int):
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk of {chunk} {self._what}")
+        self.reset()
+        T = x.shape[-1]
+        full = T - T % chunk
+        outs = [self.push(x[..., i:i + chunk]) for i in range(0, full, chunk)]
+        outs.append(self.finish(x[..., full:]))
+        return torch.cat(outs, dim=2)
+
+
+class LookaheadEncoder(_LookaheadStream):
+    """Streams ANY BigCodecEncoder whose look-ahead is finite (causal or non-causal convs, a unidirectional ResLSTM, no
+    anti-aliasing), exactly, with the fixed algorithmic delay `lookahead` (samples):
+
+        la = LookaheadEncoder(encoder)
+        z = la.push(x)        # x (B, 1, n), n a positive multiple of the hop -> (B, D, f): the f >= 0 frames now final
+        z = la.finish(x)      # an optional last chunk of any length >= 0; flushes and returns the remaining frames
+        la.reset()            # a new stream; push after finish raises RuntimeError until then
+        z = la.encode(x, chunk)   # a whole clip in chunks + finish: the memory of one chunk, not of the clip
+
+    cat(pushes..., finish) equals encoder(x) on the whole input (bit for bit in x6 and bf16; to fp32 rounding in h3,
+    whose block scales depend on the tiling).  Every stage is a lazy valid conv over [carry | new] (_stage_row); one
+    bc_stream_window_la launch forms the window (the stage's Snake applied on load) and the next carry.  A ResidualUnit
+    the one-launch kernel serves runs over its RAW window with its own padding and returns the exact columns as a view;
+    the others run conv7 over the activated window and conv1 with the residual from the raw one.  A stage with nothing
+    to emit launches no conv.  No torch compute kernel runs in a push.  On a causal model the look-ahead is 0, every push
+    returns n / hop frames equal to StreamingEncoder's and finish() returns an empty tensor.  All rows of a stream share
+    one length; pools and HIP-graph capture are not offered (the shapes change during the first pushes)."""
+
+    def encode(self, x, chunk: int) -> torch.Tensor:
+        """A whole clip through push in chunks of `chunk` samples (a multiple of the hop) and finish for the rest:
+        encoder(x), with the activations of one chunk in memory at a time."""
+        return self._chunked(x, chunk)
+
+
+class LookaheadDecoder(_LookaheadStream):
+    """LookaheadEncoder's counterpart for any BigCodecDecoder: push(z (B, D, n) post-VQ frames) returns the (B, 1, m)
+    samples that are now final, finish(z=None) the rest; cat(pushes..., finish) equals decoder(z, vq=False).
+    tokens(codes (B, n, Nq) int64 device) pushes index frames (vq2emb first).  A non-causal transposed conv (k = 2s,
+    padding p) carries one input frame: with N frames seen its outputs o < N s - p are final, emitted through
+    conv_transpose1d's own output length and crop; the last p come at the flush.  `lookahead` is in samples."""
+
+    _what = "frames"
+
+    def _count(self, n_in: int, n_out: int):
+        self.samples += n_out
+
+    def tokens(self, codes) -> torch.Tensor:
+        return self.push(self.model.tokens_to_latent(codes))
+
+    def decode(self, z, chunk: int) -> torch.Tensor:
+        """A whole latent sequence through push in chunks of `chunk` frames and finish for the rest."""
+        return self._chunked(z, chunk)
 
 
 def plan_rows(entries):

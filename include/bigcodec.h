@@ -292,6 +292,22 @@ int bc_stream_window(const float* x, long long x_batch_stride, long long x_row_s
                      const float* snake_alpha_exp, const float* snake_inv_beta, float* win, float* ctx_out, int B, int C,
                      int n, int P, void* stream);
 
+/* bc_stream_window_la: bc_stream_window for a look-ahead stream (streaming.py LookaheadEncoder / LookaheadDecoder,
+ *   DESIGN.md §23; the reference has no streaming mode: its whole-sequence non-causal convs, vq/module.py:59-72 with
+ *   symmetric padding, define the result).  A stage of such a stream is a lazy valid conv whose carried input grows and
+ *   shrinks and whose right zero padding arrives at the flush, so the carry read (Pin columns) and the carry stored
+ *   (Pout columns) differ and R zero columns may follow: for each row (b, c), with S = Pin + n,
+ *   win[b][c][j] = j < Pin ? ctx[b][c][j] : j < S ? act(x[b][c][j - Pin]) : 0.0f for j < S + R, and
+ *   ctx_out[b][c][i] = win[b][c][S - Pout + i] for i < Pout, Pout <= S (it may reach back into ctx, never into the
+ *   zeros).  act, ctx NULL (zeros) and the strides as in bc_stream_window; win is [B][C][S + R], ctx [B][C][Pin],
+ *   ctx_out [B][C][Pout], NULL exactly when Pout == 0, and must not overlap ctx.  n == 0 is legal when Pin + R > 0 (a
+ *   flush without new input; x is then not read and may be NULL).  Pin == Pout, R == 0 reproduces bc_stream_window bit
+ *   for bit.  Returns 1 for a null pointer or inconsistent sizes (an empty window, Pout > Pin + n, a ctx_out that
+ *   disagrees with Pout), 3 when B * C or Pin + n + R exceeds 2^31 - 1, 0 without a launch when B == 0. */
+int bc_stream_window_la(const float* x, long long x_batch_stride, long long x_row_stride, const float* ctx,
+                        const float* snake_alpha_exp, const float* snake_inv_beta, float* win, float* ctx_out, int B,
+                        int C, int n, int Pin, int R, int Pout, void* stream);
+
 /* bc_stream_window_slots: bc_stream_window for a pool of independent streaming sessions (streaming.py StreamPool).  It
  *   stands in for no reference behaviour: the reference has no streaming, and its whole-sequence causal pass defines
  *   each session's result, as for bc_stream_window.  The contexts live in pool[pool_rows][C][P]; the DEVICE arrays

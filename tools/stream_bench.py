@@ -12,6 +12,9 @@ pool (StreamPool), through one batched stream and through B single streams (DESI
 --pool --ragged [--decode] [--pool-B 16 64] times a tick in which every session has its own number of hops ready (1 to
 5, drawn per tick with a fixed seed): one push with `hops` against one equal-length push per distinct length
 (DESIGN.md §20).
+--lookahead [--pool-B 1 16] [--la-hops 1 5 25] streams the NON-causal `default` encoder through LookaheadEncoder
+(DESIGN.md §23): ms per push at each chunk length, and the clip-level cost of la.encode(x, chunk) over the
+whole-sequence encoder(x) on the same --seconds clip.
 """
 import argparse
 import os
@@ -147,8 +150,50 @@ def ragged_leg(a, dev, enc, dec):
                               grouped_over_ragged=round(best["grouped"] / best["ragged"], 2))), flush=True)
 
 
+def lookahead_leg(a, dev):
+    """--lookahead: the non-causal `default` encoder, current precision (x6 unless BIGCODEC_PRECISION says otherwise).
+    Per (B, hops per push): la.encode(x, chunk) and encoder(x) on the same clip, alternating, one untimed pass of each
+    first (it warms every window shape of the transient as well as the steady ones), then --reps timed passes of each,
+    HIP-synchronised around a pass; medians.  ms per push = the stream's clip time over its pushes (the finish counts
+    as one).  One JSON line per (B, hops)."""
+    import json
+    import statistics
+
+    from audiotokenization_amd import _lib as L
+    from audiotokenization_amd import streaming as S
+
+    enc, _ = build_model_pair("default", device=dev)
+    hop = int(enc.hop_length)
+    n = int(a.seconds * 24000) // hop * hop
+    la = S.LookaheadEncoder(enc)
+    for B in a.pool_B:
+        x = synth_batch(B, n, 0, dev)
+        for hops in a.la_hops:
+            chunk = hops * hop
+            times = {"stream": [], "whole": []}
+            with torch.no_grad():
+                equal = bool(torch.equal(la.encode(x, chunk), enc(x)))
+                for _ in range(a.reps):
+                    for name, fn in (("stream", lambda: la.encode(x, chunk)), ("whole", lambda: enc(x))):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        times[name].append(1e3 * (time.perf_counter() - t0))
+            med = {k: statistics.median(v) for k, v in times.items()}
+            pushes = n // chunk + 1
+            print(json.dumps(dict(leg="lookahead", model="default", precision=L.precision_name(), B=B, hops=hops,
+                                  seconds=n / 24000, lookahead_samples=la.lookahead, pushes=pushes,
+                                  ms_per_push=round(med["stream"] / pushes, 4), stream_ms=round(med["stream"], 2),
+                                  whole_ms=round(med["whole"], 2), ratio=round(med["stream"] / med["whole"], 3),
+                                  stream_ms_all=[round(t, 2) for t in times["stream"]],
+                                  whole_ms_all=[round(t, 2) for t in times["whole"]], equal=equal)), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
+    p.add_argument("--lookahead", action="store_true", help="LookaheadEncoder on the non-causal default model")
+    p.add_argument("--la-hops", type=int, nargs="+", default=[1, 5, 25], help="--lookahead: hops per push")
     p.add_argument("--pool", action="store_true", help="session-pool push vs one batched stream vs B single streams")
     p.add_argument("--pool-B", type=int, nargs="+", default=[16, 64])
     p.add_argument("--pool-frames", type=int, nargs="+", default=[1, 5], help="frames (hops) per session and tick")
@@ -169,6 +214,8 @@ def main():
     else:
         from audiotokenization_amd import streaming as S
     dev = torch.device("cuda:0")
+    if a.lookahead:
+        return lookahead_leg(a, dev)
     enc, dec = build_model_pair("default", device=dev, causal=True)
     if a.pool:
         return (ragged_leg if a.ragged else pool_leg)(a, dev, enc, dec)
