@@ -11,8 +11,10 @@ from .lightning_shim import CodecLightningModule
 from .blocks import DecoderBlock, EncoderBlock, ResidualUnit, ResLSTM
 from .conv import WNConv1d, WNConvTranspose1d
 from .modules import Activation1d, FactorizedVectorQuantize, ResidualVQ, SnakeBeta
+from .streaming import LookaheadPool
 
 __all__ = [
+    "LookaheadPool",
     "BigCodecEncoder", "BigCodecDecoder", "CodecLightningModule", "AttrDict", "load_config", "preset",
     "Activation1d", "DecoderBlock", "EncoderBlock", "FactorizedVectorQuantize", "ResidualUnit", "ResidualVQ",
     "ResLSTM", "SnakeBeta",

@@ -66,6 +66,7 @@ _SIGS = {
     "bc_stream_window_la": (I, [P, L, L, P, P, P, P, P, I, I, I, I, I, I, P]),
     "bc_stream_window_slots": (I, [P, L, L, P, P, P, P, P, P, I, I, I, I, I, P]),
     "bc_stream_window_slots_lens": (I, [P, L, L, P, P, P, P, I, P, P, P, I, I, I, I, I, P]),
+    "bc_stream_window_slots_la": (I, [P, L, L, I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "bc_lstm_state_gather": (I, [P, P, P, P, P, I, I, I, I, P]),
     "bc_lstm_state_scatter": (I, [P, P, P, P, P, I, I, I, I, P]),
     "bc_zero_tail": (I, [P, P, P, I, I, L, L, P]),

@@ -670,6 +670,15 @@ int bc_stream_window_slots_lens(const float* x, long long x_batch_stride, long l
                                          snake_inv_beta, win, B, C, n, P, pool_rows, S(stream));
 }
 
+int bc_stream_window_slots_la(const float* x, long long x_batch_stride, long long x_row_stride, int x_cols, float* pool,
+                              const int* src, const int* dst, const int* cin, const int* n, const int* xoff,
+                              const int* keep, const int* cout, const float* snake_alpha_exp,
+                              const float* snake_inv_beta, float* win, int B, int C, int W, int Pmax, int pool_rows,
+                              void* stream) {
+  return stream_window_slots_la_launch(x, x_batch_stride, x_row_stride, x_cols, pool, src, dst, cin, n, xoff, keep, cout,
+                                       snake_alpha_exp, snake_inv_beta, win, B, C, W, Pmax, pool_rows, S(stream));
+}
+
 int bc_lstm_state_gather(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0, int num_layers,
                          int H, int B, int pool_rows, void* stream) {
   return lstm_state_gather_launch(h_pool, c_pool, src, h0, c0, num_layers, H, B, pool_rows, S(stream));

@@ -101,6 +101,10 @@ int stream_window_slots_launch(const float* x, long long xbs, long long xT, floa
 int stream_window_slots_lens_launch(const float* x, long long xbs, long long xT, float* pool, const int* src,
                                     const int* dst, const int* lens, int unit, const float* sa, const float* sb,
                                     float* win, int B, int C, int n, int P, int pool_rows, hipStream_t st);
+int stream_window_slots_la_launch(const float* x, long long xbs, long long xT, int xn, float* pool, const int* src,
+                                  const int* dst, const int* cin, const int* nnew, const int* xoff, const int* keep,
+                                  const int* cout, const float* sa, const float* sb, float* win, int B, int C, int W,
+                                  int Pmax, int pool_rows, hipStream_t st);
 int lstm_state_gather_launch(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0,
                              int num_layers, int H, int B, int pool_rows, hipStream_t st);
 int lstm_state_scatter_launch(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT,

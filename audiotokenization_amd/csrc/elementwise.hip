@@ -403,6 +403,70 @@ int stream_window_slots_lens_launch(const float* x, long long xbs, long long xT,
   return BC_OK;
 }
 
+// Look-ahead session pool (streaming.py LookaheadPool): stream_window_la_kernel's window (carry in and
+// carry out of different lengths, zeros behind) over stream_window_slots_lens_kernel's pool rows (src / dst, a length
+// per entry), plus an input offset per entry.  Every stage's window is left-aligned and ragged: entry b's row is
+// [its cin[b] carried columns | its n[b] new columns, read from x at column xoff[b] on | zeros up to W], and the
+// carry it stores is cout[b] columns of that row from column keep[b] on.  A stage's right zero padding at the flush
+// and the zero tail behind a short entry are the same literal zeros, so flushing and pushing entries share a launch.
+// pool is [pool_rows][C][Pmax]: Pmax is the row pitch, an entry uses the first cin / cout columns of its rows.
+// src[b] < 0 reads the cin[b] carried columns as zeros (a fresh session: its left zero padding); dst[b] < 0 or
+// cout[b] == 0 stores nothing.  cin and cout are clamped to [0, Pmax], xoff to [0, xn] and n to [0, min(W - cin,
+// xn - xoff)], so no index array can take an access out of x, win or a pool row; x is never read outside
+// [xoff, xoff + n).  Same src / dst contract (the HOST keeps the two row sets disjoint), same snake(), same strided x,
+// same 2-D grid and one float per lane as the neighbours (Pin = 6, 18, 54: no 16-byte path fits, see above).
+__global__ void __launch_bounds__(256) stream_window_slots_la_kernel(
+    const float* __restrict__ x, long long xbs, long long xT, int xn, float* pool, const int* __restrict__ src,
+    const int* __restrict__ dst, const int* __restrict__ cin, const int* __restrict__ nnew,
+    const int* __restrict__ xoff, const int* __restrict__ keep, const int* __restrict__ cout,
+    const float* __restrict__ sa, const float* __restrict__ sb, float* __restrict__ win, int C, int W, int Pmax, int rows,
+    int pool_rows) {
+  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
+    const int b = row / C, c = row - b * C;
+    const int s = src[b], d = dst[b], k = keep[b];
+    const int ci = min(max(cin[b], 0), Pmax), co = min(max(cout[b], 0), Pmax);
+    const int xo = min(max(xoff[b], 0), xn);
+    const int n = min(max(nnew[b], 0), min(W - ci, xn - xo));  // (W - ci < 0: no new column, the carry fills the row)
+    const int S = ci + n;
+    const float* xr = x + (long long)b * xbs + (long long)c * xT + xo;
+    float* wr = win + (long long)row * W;
+    const float* cr = (s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * Pmax : nullptr;
+    float* nr = (d >= 0 && co > 0 && BC_DOK(d < pool_rows)) ? pool + ((long long)d * C + c) * Pmax : nullptr;
+    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
+      float v = 0.f;
+      if (j < ci) {
+        if (cr && BC_DOK(j >= 0 && j < Pmax)) v = cr[j];
+      } else if (j < S) {
+        if (BC_DOK(j - ci >= 0 && xo + (j - ci) < xn && xo + (j - ci) < xT)) {
+          v = xr[j - ci];
+          if (sa) v = snake(v, a_, b_);
+        }
+      }
+      if (BC_DOK(j >= 0 && j < W && row < rows)) wr[j] = v;
+      if (nr && j >= k && j - k < co && BC_DOK(j - k >= 0 && j - k < Pmax && j < S)) nr[j - k] = v;
+    }
+  }
+}
+
+int stream_window_slots_la_launch(const float* x, long long xbs, long long xT, int xn, float* pool, const int* src,
+                                  const int* dst, const int* cin, const int* nnew, const int* xoff, const int* keep,
+                                  const int* cout, const float* sa, const float* sb, float* win, int B, int C, int W,
+                                  int Pmax, int pool_rows, hipStream_t st) {
+  if (!pool || !src || !dst || !cin || !nnew || !xoff || !keep || !cout || !win) return BC_ERR_ARG;
+  if (B < 0 || C < 1 || W < 1 || Pmax < 1 || pool_rows < 1 || xn < 0) return BC_ERR_ARG;
+  if (xn > 0 && (!x || xT < xn || xbs < (long long)(C - 1) * xT + xn)) return BC_ERR_ARG;
+  if ((sa == nullptr) != (sb == nullptr)) return BC_ERR_ARG;
+  const long long rows = (long long)B * C;
+  if (rows > 0x7fffffffLL || (long long)pool_rows * C > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
+  if (rows == 0) return BC_OK;
+  const int gx = (int)std::min<long long>(((long long)W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
+  hipLaunchKernelGGL(stream_window_slots_la_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, xn, pool, src, dst, cin,
+                     nnew, xoff, keep, cout, sa, sb, win, C, W, Pmax, (int)rows, pool_rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
+}
+
 // The carried ResLSTM state of a session pool: bc_reslstm_fwd_state takes dense [num_layers][H][B] (unit-major) h0 / c0
 // and hands back hT / cT; the pool keeps [num_layers][H][pool_rows].  Gather: h0[lu][b] = src[b] >= 0 ?
 // h_pool[lu][src[b]] : 0 (a fresh session's zero state), c likewise; scatter: h_pool[lu][dst[b]] = hT[lu][b] for

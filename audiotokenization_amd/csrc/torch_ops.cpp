@@ -514,6 +514,40 @@ Tensor stream_window_slots_lens_(const Tensor& x, const Tensor& pool, const Tens
   return win;
 }
 
+// ---- stream_window_slots_la_: the left-aligned ragged window of a look-ahead pool's stage (streaming.py LookaheadPool):
+// seven int32 (B,) device arrays per launch; x may have no columns (a push in which this stage only flushes) -------
+Tensor stream_window_slots_la_(const Tensor& x, const Tensor& pool, const Tensor& src, const Tensor& dst,
+                               const Tensor& cin, const Tensor& n, const Tensor& xoff, const Tensor& keep,
+                               const Tensor& cout, const optional<Tensor>& a, const optional<Tensor>& ib, int64_t W) {
+  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && (x.size(2) == 0 || x.stride(2) == 1),
+                    "bigcodec::stream_window_slots_la_: x must be a (B, C, n) float32 tensor with unit time stride");
+  const int64_t B = x.size(0), C = x.size(1), xn = x.size(2);
+  TORCH_CHECK_VALUE(W >= 1, "bigcodec::stream_window_slots_la_: a non-empty window (W >= 1)");
+  check_coeffs(a, ib, C, "stream_window_slots_la_");
+  dev(pool, "pool");
+  same_device(x, pool, "pool");
+  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && pool.size(2) >= 1,
+                    "bigcodec::stream_window_slots_la_: pool must be (rows, C, Pmax), Pmax >= 1");
+  const char* op = "stream_window_slots_la_";
+  const int* ps = slots(x, src, B, op, "src");
+  const int* pd = slots(x, dst, B, op, "dst");
+  const int* pci = slots(x, cin, B, op, "cin");
+  const int* pn = slots(x, n, B, op, "n");
+  const int* pxo = slots(x, xoff, B, op, "xoff");
+  const int* pk = slots(x, keep, B, op, "keep");
+  const int* pco = slots(x, cout, B, op, "cout");
+  auto win = at::empty({B, C, W}, x.options());
+  if (B == 0) return win;
+  const int64_t xT = xn && C > 1 ? x.stride(1) : xn, xbs = xn && B > 1 ? x.stride(0) : C * xT;  // (size-1 dims: any stride)
+  ok(bc_stream_window_slots_la(xn ? x.data_ptr<float>() : nullptr, xbs, xT, i32(xn, "x columns"), pool.data_ptr<float>(),
+                               ps, pd, pci, pn, pxo, pk, pco, optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
+                               win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(W, "W"), i32(pool.size(2), "Pmax"),
+                               i32(pool.size(0), "pool rows"), stream_of(x)),
+     "bc_stream_window_slots_la");
+  return win;
+}
+
 std::vector<Tensor> lstm_state_gather(const Tensor& h_pool, const Tensor& c_pool, const Tensor& src, int64_t B) {
   dev(h_pool, "h_pool");
   dev(c_pool, "c_pool");
@@ -770,6 +804,8 @@ TORCH_LIBRARY(bigcodec, m) {
         "int P) -> Tensor");
   m.def("stream_window_slots_lens_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor lens, int unit, "
         "Tensor? alpha_exp, Tensor? inv_beta, int P) -> Tensor");
+  m.def("stream_window_slots_la_(Tensor x, Tensor(a!) pool, Tensor src, Tensor dst, Tensor cin, Tensor n, Tensor xoff, "
+        "Tensor keep, Tensor cout, Tensor? alpha_exp, Tensor? inv_beta, int W) -> Tensor");
   m.def("reslstm_lens(Tensor x, Tensor[] w_ih_packed, Tensor[] bias, Tensor[] w_hh_packed, Tensor? out_alpha_exp, "
         "Tensor? out_inv_beta, int mode, Tensor? h0, Tensor? c0, Tensor lens) -> Tensor[]");
   m.def("lstm_state_gather(Tensor h_pool, Tensor c_pool, Tensor src, int B) -> Tensor[]");
@@ -806,6 +842,7 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("stream_window_la", &Guarded<&stream_window_la>::call);
   m.impl("stream_window_slots_", &Guarded<&stream_window_slots_>::call);
   m.impl("stream_window_slots_lens_", &Guarded<&stream_window_slots_lens_>::call);
+  m.impl("stream_window_slots_la_", &Guarded<&stream_window_slots_la_>::call);
   m.impl("reslstm_lens", &Guarded<&reslstm_lens>::call);
   m.impl("lstm_state_gather", &Guarded<&lstm_state_gather>::call);
   m.impl("lstm_state_scatter_", &Guarded<&lstm_state_scatter_>::call);

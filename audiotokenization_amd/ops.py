@@ -27,7 +27,7 @@ _ns = None
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
        "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_",
-       "stream_window_slots_lens_", "reslstm_lens", "stoi", "stream_window_la")
+       "stream_window_slots_lens_", "reslstm_lens", "stoi", "stream_window_la", "stream_window_slots_la_")
 
 
 def load():
@@ -166,6 +166,10 @@ def _register_fakes():
     def _stream_window_slots_lens(x, pool, src, dst, lens, unit, a, ib, P):
         B, C, n = x.shape
         return _new(x, (B, C, P + n))
+
+    @reg("bigcodec::stream_window_slots_la_")
+    def _stream_window_slots_la(x, pool, src, dst, cin, n, xoff, keep, cout, a, ib, W):
+        return _new(x, (x.shape[0], x.shape[1], W))
 
     @reg("bigcodec::reslstm_lens")
     def _reslstm_lens(x, w_ih, bias, w_hh, sa, sb, mode, h0, c0, lens):

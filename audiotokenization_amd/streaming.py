@@ -39,6 +39,10 @@ symmetric padding is a causal conv whose output arrives late, so every stage run
 (bc_stream_window_la), emits what is final and holds the rest; finish() flushes each layer's own right zero padding.  The
 result equals the whole-sequence forward after a fixed look-ahead (lookahead_samples: 2451 samples for `default`).  The
 classes above keep refusing non-causal models.
+
+LookaheadPool is StreamPool for those models: every stage's window is left-aligned and ragged per
+session (bc_stream_window_slots_la: a carry length, a new length, an input offset and a stored carry per entry), so
+sessions in their transient, in steady state and at their flush share one batched push.
 """
 from __future__ import annotations
 
@@ -568,7 +572,8 @@ class LookaheadEncoder(_LookaheadStream):
     the others run conv7 over the activated window and conv1 with the residual from the raw one.  A stage with nothing
     to emit launches no conv.  No torch compute kernel runs in a push.  On a causal model the look-ahead is 0, every push
     returns n / hop frames equal to StreamingEncoder's and finish() returns an empty tensor.  All rows of a stream share
-    one length; pools and HIP-graph capture are not offered (the shapes change during the first pushes)."""
+    one length and start together; LookaheadPool serves independent sessions with ragged windows in one batched push.
+    HIP-graph capture is not offered."""
 
     def encode(self, x, chunk: int) -> torch.Tensor:
         """A whole clip through push in chunks of `chunk` samples (a multiple of the hop) and finish for the rest:
@@ -871,6 +876,380 @@ class StreamPool:
     def graph(self, B: int, n: int) -> "PoolGraph":
         """One pool push of up to B sessions and chunks of n samples (encoder) / frames (decoder) as a HIP graph."""
         return PoolGraph(self, B, n)
+
+
+# ---- look-ahead session pool: many non-causal streams in one batched push (DESIGN.md §24) -----------------------------
+#
+# §23's window is dense: [carry | new | right zeros] with one carry length for the whole batch, which is why its rows
+# must start together.  Here every stage's window is LEFT-ALIGNED AND RAGGED per entry: entry b's row is its own carry,
+# its own new columns and zeros up to the widest row.  The zeros behind a short entry and a flushing entry's right zero
+# padding are the same literal zeros, so sessions in their transient, in steady state and at their flush share every
+# launch; they differ in how many output columns the host claims for them (_stage_row, per entry).
+
+class LookaheadSlots:
+    """The host side of a LookaheadPool, for any list of lazy stages (tests run it on a toy stack without a GPU): the
+    slot table, each session's per-stage stream states (_stage_row's) and per-stage ping-pong phases, and the plan of
+    one push: per stage the index arrays bc_stream_window_slots_la / the ResLSTM gather, scatter and lens take.
+
+    The phase is kept per slot AND per stage (None: nothing stored yet, the stage reads zeros through src = -1): a
+    stage that receives nothing for an entry this push stores nothing (dst = -1) and keeps its phase, so its carry
+    stays where it is.  Slot s owns pool rows 2s and 2s + 1 of every stage; a stage's src rows are the current phases
+    and its dst rows the other ones, so with distinct slots the two sets are disjoint and dst holds no row twice."""
+
+    def __init__(self, stages, capacity: int):
+        self.stages = list(stages)
+        if not self.stages or self.stages[-1].kind == "convT":
+            raise NotImplementedError("a look-ahead pool needs a model that ends in a conv (a transposed conv's crop "
+                                      "differs per entry and is resolved by the next stage's window)")
+        if any(a.kind == "convT" and b.kind == "lstm" for a, b in zip(self.stages, self.stages[1:])):
+            raise NotImplementedError("a ResLSTM directly behind a transposed conv: its rows would not be left-aligned")
+        self.table = SlotTable(capacity)
+        self.states = [None] * self.table.capacity
+        self.phases = [None] * self.table.capacity
+
+    def pitch(self, j: int) -> int:
+        """Pmax of stage j's pool rows: the largest carry it can hold ((k - 1) d columns; hist frames)."""
+        st = self.stages[j]
+        return max(1, st.hist if st.kind == "convT" else (st.k - 1) * st.d)
+
+    def open(self) -> int:
+        s = self.table.open()
+        self.states[s] = [st.start() for st in self.stages]
+        self.phases[s] = [None] * len(self.stages)
+        return s
+
+    def plan(self, sids, lens, flush):
+        """One push of lens[i] input columns for session sids[i] (flush[i]: then its flush).  Pure: nothing changes
+        until commit().  Returns a namespace: stages[j] (kind, launch, the per-entry lists src, dst, cin, n, xoff, keep,
+        cout, out, and W, Wraw, crop, tout), rows[i][j] (_stage_row's rows of entry i), counts[i] (the last stage's
+        outputs), and the next states and phases."""
+        import types
+
+        m = len(sids)
+        new, xoff = [int(n) for n in lens], [0] * m
+        states = [list(self.states[s]) for s in sids]
+        phases = [list(self.phases[s]) for s in sids]
+        rows, out_stages = [[] for _ in sids], []
+        for j, st in enumerate(self.stages):
+            p = types.SimpleNamespace(kind=st.kind, launch=False, src=[-1] * m, dst=[-1] * m, cin=[0] * m, n=[0] * m,
+                                      xoff=[0] * m, keep=[0] * m, cout=[0] * m, out=[0] * m, W=0, Wraw=0, crop=0, tout=0)
+            crops = [0] * m
+            for b, s in enumerate(sids):
+                carry, seen, emitted = states[b][j]
+                row, states[b][j] = _stage_row(st, states[b][j], new[b], bool(flush[b]))
+                rows[b].append(row)
+                cin, nb, R, out, cout = row
+                p.out[b] = out
+                if not (nb or out):  # nothing arrived and nothing to flush: a padding row; carry and phase stay
+                    continue
+                p.launch = True
+                ph = phases[b][j]
+                if st.kind == "lstm":
+                    p.src[b] = -1 if ph is None else 2 * s + ph
+                    ph = phases[b][j] = 0 if ph is None else 1 - ph
+                    p.dst[b], p.n[b] = 2 * s + ph, nb
+                    continue
+                p.src[b] = 2 * s + ph if ph is not None and cin else -1
+                p.cin[b], p.n[b], p.xoff[b], p.cout[b] = cin, nb, xoff[b], cout
+                p.keep[b] = cin + nb - cout if st.kind == "convT" else out * st.s
+                if cout:
+                    ph = phases[b][j] = 0 if ph is None else 1 - ph
+                    p.dst[b] = 2 * s + ph
+                p.Wraw, p.W = max(p.Wraw, cin + nb), max(p.W, cin + nb + R)
+                if st.kind == "convT" and out:  # (_LookaheadStream._run_convT: the window's own column of output `emitted`)
+                    crops[b] = emitted + st.pl - (seen - cin) * st.s
+            if st.kind == "convT" and any(p.out):
+                p.crop = min(c for c, o in zip(crops, p.out) if o)
+                p.tout = max(c + o for c, o in zip(crops, p.out) if o) - p.crop
+                xoff = [c - p.crop if o else 0 for c, o in zip(crops, p.out)]
+            else:
+                p.tout, xoff = max(p.out), [0] * m
+            new = list(p.out)
+            out_stages.append(p)
+        return types.SimpleNamespace(sids=list(sids), lens=[int(n) for n in lens], flush=[bool(f) for f in flush],
+                                     stages=out_stages, rows=rows, counts=new, states=states, phases=phases)
+
+    def commit(self, plan, samples) -> None:
+        """The plan was executed: its states and phases become the sessions'; flushed sessions are closed."""
+        self.table.commit(plan.sids, samples)
+        for b, s in enumerate(plan.sids):
+            self.states[s], self.phases[s] = plan.states[b], plan.phases[b]
+            if plan.flush[b]:
+                self.table.close(s)
+
+
+class LookaheadPool:
+    """Many independent look-ahead streams of a NON-causal (or causal) model in one batched push: StreamPool for the
+    models LookaheadEncoder / LookaheadDecoder accept.
+
+        pool = LookaheadPool(model, capacity)      # lookahead_stages' refusals
+        sid = pool.open(); pool.close(sid); pool.live(); pool.samples(sid); pool.state_bytes(); pool.lookahead
+        y, counts = pool.push(sids, x, hops=None)  # x (m, 1, n) samples / (m, D, n) frames; hops as StreamPool's
+        y, counts = pool.tokens(sids, codes, hops=None)   # decoder pools: codes (m, n, Nq) int64 on the device
+        y, counts = pool.finish(sids, x=None, lens=None)  # optional last chunks of ANY length >= 0, then the flush
+
+    y has the padded shape: entry i's first counts[i] columns are the frames / samples now FINAL for sids[i] (counts[i]
+    may be 0: the look-ahead holds them back), the rest is exactly zero (one bc_zero_tail).  counts is a host list
+    taken from the plan: no device read.  Per session, cat(y[i, :, :counts[i]] over its pushes and its finish) equals
+    the whole-sequence forward on its own data and its own B = 1 look-ahead stream (bit for bit in x6; to fp32
+    rounding in h3), whatever else is in the push: sessions open at any tick, sit ticks out, deliver their own number
+    of hops, and one in its transient shares the launch with one in steady state and one at its flush.  finish()
+    closes its sessions: their slots are free again.  push(..., finish=[...]) (one bool per entry) flushes the marked
+    entries after their hops in the same launches as the others' push; finish() is that for every entry, with lengths
+    that need not be multiples of the hop.
+
+    Every stage runs ONCE per push on the batch: one bc_stream_window_slots_la launch forms the left-aligned ragged
+    windows [carry | new | zeros] and stores each entry's next carry to its pool row, then the stage's own kernel runs
+    over the dense batch (Conv1dWN.run without padding; the one-launch ResidualUnit over the raw window with its own
+    padding, its exact columns handed on as a view; conv_transpose1d with the smallest crop of the batch, each entry's
+    own crop becoming the next window's input offset; the ResLSTM between one state gather and one scatter, with each
+    entry's own length).  All index arrays of all stages ride in one pinned buffer and one non-blocking copy per push.
+    A stage no entry feeds launches nothing.  All per-session arithmetic is _stage_row (LookaheadSlots.plan).
+
+    Refused on the host before any launch, as in StreamPool: an unknown, closed or repeated session id, an empty push,
+    a batch dimension other than len(sids), a wrong channel count, a chunk that is no positive multiple of the hop,
+    `hops` / `lens` / `finish` of another length or with a bad entry (ValueError); a precision other than the one of the
+    pool's first push (RuntimeError).  A push that raises later leaves ITS sessions undefined: close them."""
+
+    def __init__(self, model, capacity: int):
+        self.model = model
+        self.decoder = hasattr(model, "tokens_to_latent")
+        self.slots = LookaheadSlots(lookahead_stages(model), capacity)
+        self.table, self.stages = self.slots.table, self.slots.stages
+        self.capacity, self.hop = self.table.capacity, int(model.hop_length)
+        self.lookahead = lookahead_samples(model)
+        self.channels = int(self.stages[0].module.in_channels)
+        self._pools = {}  # stage -> its (2 * capacity, C, Pmax) carries, or the ResLSTM's two (layers, H, 2 * capacity)
+        self._mode = None  # the precision of the pool's first push
+        self._pinned = self._event = None
+        self.plan = None  # the plan of the last push (tests compare its rows with lookahead_plan's)
+
+    # ---- sessions ------------------------------------------------------------------------------------------------
+    def open(self) -> int:
+        return self.slots.open()
+
+    def close(self, sid) -> None:
+        self.table.close(sid)
+
+    def live(self):
+        """The open session ids, ascending."""
+        return self.table.live()
+
+    def samples(self, sid) -> int:
+        """Samples session `sid` has consumed (encoder pools) or produced (decoder pools) so far."""
+        self.table.check([sid], 1, allow_undefined=True)
+        return self.table.samples[sid]
+
+    def state_bytes(self) -> int:
+        """Bytes of device state the pool holds (both ping-pong rows of every slot; 0 before the first push)."""
+        return sum(t.numel() * 4 for v in self._pools.values() for t in (v if isinstance(v, tuple) else (v,)))
+
+    # ---- pushes --------------------------------------------------------------------------------------------------
+    def _admit(self, sids, shape, flush: bool, channels=None):
+        sids = self.table.check(sids, self.capacity)
+        channels = self.channels if channels is None else channels
+        if len(shape) != 3 or shape[0] != len(sids):
+            raise ValueError(f"input of shape {tuple(shape)} for {len(sids)} sessions: row i belongs to sids[i]")
+        if channels and shape[1] != channels:
+            raise ValueError(f"input of shape {tuple(shape)}: expected {channels} channels")
+        if not flush and (shape[2] < 1 or (not self.decoder and shape[2] % self.hop)):
+            raise ValueError(f"chunk of {shape[2]} samples: must be a positive multiple of the hop ({self.hop}); "
+                             "finish() takes any length")
+        if self._mode is not None and _lib.precision_mode() != self._mode:
+            raise RuntimeError(f"precision changed ({self._mode} -> {_lib.precision_mode()}): the pool's carried state "
+                               "belongs to the mode of its first push")
+        return sids
+
+    @staticmethod
+    def _ints(values, entries: int, lo: int, hi: int, what: str):
+        values = list(values)
+        if len(values) != entries:
+            raise ValueError(f"{len(values)} {what} for {entries} sessions: entry i belongs to sids[i]")
+        for v in values:
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"{what} entry {v!r}: an int from {lo} to {hi}")
+        return values
+
+    def _lens(self, sids, n: int, hops):
+        """The input columns per entry of a push of n columns with `hops` (StreamPool's: ints in [1, n_hops])."""
+        unit = 1 if self.decoder else self.hop
+        if hops is None:
+            return [n] * len(sids)
+        return [h * unit for h in self._ints(hops, len(sids), 1, n // unit, "hops")]
+
+    def _flags(self, sids, finish):
+        if finish is None:
+            return [False] * len(sids)
+        finish = list(finish)
+        if len(finish) != len(sids) or not all(isinstance(f, bool) for f in finish):
+            raise ValueError(f"finish must hold one bool per session (got {finish!r} for {len(sids)} sessions)")
+        return finish
+
+    def push(self, sids, x, hops=None, finish=None):
+        sids = self._admit(sids, x.shape, False)
+        lens = self._lens(sids, x.shape[2], hops)
+        return self._run(sids, x, lens, self._flags(sids, finish))
+
+    def tokens(self, sids, codes, hops=None, finish=None):
+        """codes (len(sids), n, Nq) int64 on the device; `hops` as in push (the index frames past an entry's own are
+        never decoded into its output)."""
+        if not self.decoder:
+            raise TypeError("tokens() needs a pool over a decoder")
+        shape = (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape
+        sids = self._admit(sids, shape, False, channels=0)
+        lens = self._lens(sids, shape[2], hops)
+        flags = self._flags(sids, finish)
+        return self._run(sids, self.model.tokens_to_latent(codes), lens, flags)
+
+    def finish(self, sids, x=None, lens=None):
+        """Optional last chunks (entry i delivers lens[i] columns of x, 0 <= lens[i] <= n, any length; None: all n),
+        then every layer's own right zero padding: the frames / samples still held back.  Closes the sessions."""
+        if x is None:
+            sids = list(sids)
+            sids = self._admit(sids, (len(sids), self.channels, 0), True)
+            if lens is not None:
+                self._ints(lens, len(sids), 0, 0, "lens")
+            dev = next(self.model.parameters()).device
+            x = torch.empty(len(sids), self.channels, 0, device=dev, dtype=torch.float32)
+        else:
+            sids = self._admit(sids, x.shape, True)
+        n = x.shape[2]
+        lens = [n] * len(sids) if lens is None else self._ints(lens, len(sids), 0, n, "lens")
+        return self._run(sids, x, lens, [True] * len(sids))
+
+    # ---- one push ------------------------------------------------------------------------------------------------
+    def _stage_copy(self, values, out) -> None:
+        """StreamPool._stage: pinned staging and a copy the host does not wait for."""
+        if self._pinned is None or self._pinned.numel() < len(values):
+            self._pinned = torch.empty(max(len(values), 8 * self.capacity * (len(self.stages) + 1)), dtype=torch.int32,
+                                       pin_memory=out.is_cuda)
+            self._event = torch.cuda.Event() if out.is_cuda else None
+        elif self._event is not None:
+            self._event.synchronize()
+        self._pinned[:len(values)] = torch.tensor(values, dtype=torch.int32)
+        out.copy_(self._pinned[:len(values)], non_blocking=True)
+        if self._event is not None:
+            self._event.record(torch.cuda.current_stream(out.device))
+
+    def _run(self, sids, x, lens, flush):
+        plan = self.slots.plan(sids, lens, flush)
+        if self._mode is None:
+            self._mode = _lib.precision_mode()
+        try:
+            if not (x.is_cuda and x.dtype == torch.float32 and (x.stride(2) == 1 or not x.shape[2])):
+                x = _as_input(x)  # (a view with unit time stride is read in place by the first window)
+            with _lib.status_scope():
+                y = self._flow(plan, x)
+                _lib.check_status()
+        except BaseException:
+            self.table.undefined.update(sids)
+            raise
+        self.slots.commit(plan, plan.counts if self.decoder else plan.lens)
+        self.plan = plan
+        return y, list(plan.counts)
+
+    def _flow(self, plan, x):
+        ns, m, dev = ops.load(), len(plan.sids), x.device
+        # every index array of every stage that launches, and the output lengths, in ONE staged copy
+        values, where = [], []
+        for p in plan.stages:
+            names = () if not p.launch else ("src", "dst", "n") if p.kind == "lstm" else \
+                ("src", "dst", "cin", "n", "xoff", "keep", "cout")
+            where.append({k: len(values) + i * m for i, k in enumerate(names)})
+            for k in names:
+                values += getattr(p, k)
+        counts_at = len(values)
+        values += plan.counts
+        idx = torch.empty(len(values), dtype=torch.int32, device=dev)
+        self._stage_copy(values, idx)
+        h = x
+        for j, (st, p) in enumerate(zip(self.stages, plan.stages)):
+            arr = {k: idx[o:o + m] for k, o in where[j].items()}
+            if st.kind == "lstm":
+                h = self._run_lstm(ns, j, st, p, arr, h)
+            elif st.kind == "convT":
+                h = self._run_convT(ns, j, st, p, arr, h)
+            elif st.kind == "unit":
+                h = self._run_unit(ns, j, st, p, arr, h)
+            else:
+                h = self._run_conv(ns, j, st, p, arr, h)
+            if h.shape[2] != p.tout:
+                raise RuntimeError(f"look-ahead pool stage {j} ({st.kind}) emitted {h.shape[2]} columns, its plan {p.tout}")
+        if h.shape[2] and min(plan.counts) < h.shape[2]:
+            ns.zero_tail_(h, None, idx[counts_at:], h.shape[2] - min(plan.counts))
+        return h
+
+    def _window(self, ns, j, p, arr, x, W: int, act=None):
+        pool = self._pools.get(j)
+        if pool is None:
+            pool = self._pools[j] = torch.empty(2 * self.capacity, x.shape[1], self.slots.pitch(j), device=x.device,
+                                                dtype=torch.float32)
+        sa, sb = act.act.coeffs(x.device) if act is not None else (None, None)
+        return ns.stream_window_slots_la_(x, pool, arr["src"], arr["dst"], arr["cin"], arr["n"], arr["xoff"], arr["keep"],
+                                          arr["cout"], sa, sb, W)
+
+    @staticmethod
+    def _empty(x, channels: int):
+        return torch.empty(x.shape[0], channels, 0, device=x.device, dtype=torch.float32)
+
+    def _run_conv(self, ns, j, st, p, arr, x):
+        c = st.module
+        if not p.launch:
+            return self._empty(x, c.out_channels)
+        win = self._window(ns, j, p, arr, x, p.W, st.act)
+        if not p.tout:
+            return self._empty(x, c.out_channels)
+        return c.run(win, None, st.epilogue, pad_left=0)  # entry b's outputs: columns [0, out_b)
+
+    def _run_unit(self, ns, j, st, p, arr, x):
+        ru = st.module
+        if not p.launch:
+            return self._empty(x, x.shape[1])
+        raw = self._window(ns, j, p, arr, x, p.Wraw)  # the raw window never carries the padding (_LookaheadStream)
+        if not p.tout:
+            return self._empty(x, x.shape[1])
+        cfg = ru._fused_cfg()
+        if cfg >= 0 and ru.snake_on_load():
+            # one launch with the unit's own padding: the zeros behind an entry's columns are its right zero padding at
+            # the flush and never reach a claimed column otherwise; entry b's outputs are the view's first out_b columns
+            y = ru._flow_fused(cfg, raw, None, True, None)[0]
+            return y[:, :, st.pl:st.pl + p.tout]
+        conv7, conv1 = _conv_of(ru.block[1]), _conv_of(ru.block[3])
+        sa, sb = ru.block[0].act.coeffs(x.device)
+        aw = ns.stream_window_la(raw, None, sa, sb, 0, p.W - p.Wraw, 0)[0]  # snake(0) = 0: the zeros stay zeros
+        t = conv7.run(aw, None, 0, ru.block[2].act.coeffs(x.device), pad_left=0)
+        res = ns.stream_window_la(raw[:, :, st.pl:st.pl + p.tout], None, None, None, 0, 0, 0)[0]
+        return conv1.run(t, res)
+
+    def _run_convT(self, ns, j, st, p, arr, x):
+        conv = st.module
+        if not p.launch:
+            return self._empty(x, conv.out_channels)
+        win = self._window(ns, j, p, arr, x, p.Wraw, st.act)
+        if not p.tout:
+            return self._empty(x, conv.out_channels)
+        phases, _, bias, cfg = conv.prepared(win.device, conv.phase_cfg(win.shape[0], win.shape[2]))
+        # one crop argument for the batch: the smallest; entry b's first output is column crop_b - crop of the result,
+        # which the next stage's window takes as xoff_b
+        return ns.conv_transpose1d(win, phases, bias, None, None, conv.out_channels, p.tout, st.k, st.s, p.crop, cfg,
+                                   False)[0]
+
+    def _run_lstm(self, ns, j, st, p, arr, x):
+        if not p.launch:
+            return x
+        m = st.module
+        if not x.is_contiguous():
+            x = ns.stream_window_la(x, None, None, None, 0, 0, 0)[0]
+        pools = self._pools.get(j)
+        if pools is None:
+            shape = (m.lstm.num_layers, x.shape[1], 2 * self.capacity)
+            pools = self._pools[j] = tuple(torch.empty(shape, device=x.device, dtype=torch.float32) for _ in "hc")
+        h0, c0 = ns.lstm_state_gather(pools[0], pools[1], arr["src"], x.shape[0])
+        # an entry without a frame this push runs one step on whatever its row holds (the kernel clamps lens to 1): its
+        # output is never claimed and its state is dropped (dst = -1)
+        y, (hT, cT) = m.run(x, state=(h0, c0), return_state=True, lens=arr["n"])
+        ns.lstm_state_scatter_(pools[0], pools[1], hT, cT, arr["dst"])
+        return y
 
 
 class PoolGraph:

@@ -337,6 +337,34 @@ int bc_stream_window_slots_lens(const float* x, long long x_batch_stride, long l
                                 const int* src, const int* dst, const int* lens, int unit, const float* snake_alpha_exp,
                                 const float* snake_inv_beta, float* win, int B, int C, int n, int P, int pool_rows,
                                 void* stream);
+/* bc_stream_window_slots_la: the window of a pool of look-ahead streams (streaming.py LookaheadPool):
+ *   bc_stream_window_la's carry in / carry out of different lengths and zeros behind, over bc_stream_window_slots_lens'
+ *   pool rows and length per entry, plus an input offset per entry.  It stands in for no reference behaviour (the
+ *   reference has no streaming; its whole-sequence non-causal pass defines each session's result).  src, dst, cin, n,
+ *   xoff, keep, cout are DEVICE arrays int32[B]; pool is [pool_rows][C][Pmax], Pmax the row pitch (the largest carry the
+ *   stage can hold); win is [B][C][W]; x has x_cols columns per row, read at x + b * x_batch_stride + c *
+ *   x_row_stride + t (floats), so a strided view works (x may be NULL when x_cols == 0).  For each row (b, c), j < W:
+ *     win[b][c][j] = j < cin[b] ? pool[src[b]][c][j] : j - cin[b] < n[b] ? act(x[b][c][xoff[b] + j - cin[b]]) : 0.0f
+ *     pool[dst[b]][c][i] = win[b][c][keep[b] + i]   for i < cout[b]   (dst[b] >= 0)
+ *   Every row is left-aligned: the zeros behind an entry are a short entry's tail and, at a flush, the layer's own
+ *   right zero padding alike.  src[b] < 0 reads the cin[b] carried columns as zeros (a fresh session's left zero
+ *   padding; a caller without one passes cin[b] == 0); dst[b] < 0 or cout[b] == 0 stores nothing.  cin and cout are
+ *   clamped to [0, Pmax], xoff to [0, x_cols] and n to [0, min(W - cin, x_cols - xoff)], on the device, so no array
+ *   value takes an access out of x, win or a pool row, and x is never read outside [xoff[b], xoff[b] + n[b]) (it may
+ *   hold NaN there).  The CALLER guarantees keep[b] + cout[b] <= cin[b] + n[b] (the carry never reaches into the
+ *   zeros), and, as for bc_stream_window_slots, that no pool row is both in src and in dst of one call and that dst
+ *   names no row twice: a row's elements are read and overwritten by different workgroups, and the kernel cannot check
+ *   it.  Slot values are not checked by the launcher (the debug build skips and counts a row >= pool_rows, and a carry
+ *   that reaches into the zeros).  act and the Snake pointers as in bc_stream_window.  Every cin == cout == Pmax, n ==
+ *   W - Pmax, xoff == 0, keep == n reproduces bc_stream_window_slots bit for bit; one entry with src < 0 or a dense
+ *   carry in its pool row reproduces bc_stream_window_la.  Returns 1 for a null pointer or inconsistent sizes (W < 1,
+ *   Pmax < 1, pool_rows < 1, x_cols < 0, strides that do not hold x_cols columns), 3 when B * C or pool_rows * C
+ *   exceeds 2^31 - 1, 0 without a launch when B == 0. */
+int bc_stream_window_slots_la(const float* x, long long x_batch_stride, long long x_row_stride, int x_cols, float* pool,
+                              const int* src, const int* dst, const int* cin, const int* n, const int* xoff,
+                              const int* keep, const int* cout, const float* snake_alpha_exp,
+                              const float* snake_inv_beta, float* win, int B, int C, int W, int Pmax, int pool_rows,
+                              void* stream);
 int bc_lstm_state_gather(const float* h_pool, const float* c_pool, const int* src, float* h0, float* c0, int num_layers,
                          int H, int B, int pool_rows, void* stream);
 int bc_lstm_state_scatter(float* h_pool, float* c_pool, const int* dst, const float* hT, const float* cT, int num_layers,

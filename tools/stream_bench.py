@@ -15,6 +15,9 @@ pool (StreamPool), through one batched stream and through B single streams (DESI
 --lookahead [--pool-B 1 16] [--la-hops 1 5 25] streams the NON-causal `default` encoder through LookaheadEncoder
 (DESIGN.md §23): ms per push at each chunk length, and the clip-level cost of la.encode(x, chunk) over the
 whole-sequence encoder(x) on the same --seconds clip.
+--pool --lookahead [--decode] [--pool-B 16 64] [--ticks 40] times a tick of B NON-causal `default` sessions that open
+at different ticks and deliver 1 to 5 hops each: one LookaheadPool push against one B = 1 look-ahead stream per session
+(DESIGN.md §24).
 """
 import argparse
 import os
@@ -190,6 +193,81 @@ def lookahead_leg(a, dev):
                                   whole_ms_all=[round(t, 2) for t in times["whole"]], equal=equal)), flush=True)
 
 
+def lookahead_pool_leg(a, dev):
+    """--pool --lookahead [--decode]: B sessions of the non-causal `default` model, session i opened at tick i mod 8 (so
+    the pool always holds sessions in their transient), each drawing 1 ... 5 hops per tick (seeded), for --ticks ticks,
+    two ways in one run (alternating, best of --reps after a warm-up round): (a) ONE LookaheadPool push per tick, (b)
+    one B = 1 LookaheadEncoder / LookaheadDecoder per session, pushed one after another (what a service over a
+    non-causal checkpoint did before).  Both walk the same per-session streams; the padded batches and the B = 1
+    chunks are assembled before the timed window.  One JSON line per B."""
+    import json
+    import random
+
+    from audiotokenization_amd import _lib as L
+    from audiotokenization_amd import streaming as S
+
+    enc, dec = build_model_pair("default", device=dev)
+    model, unit = (dec, 1) if a.decode else (enc, int(enc.hop_length))
+    stream_cls = S.LookaheadDecoder if a.decode else S.LookaheadEncoder
+    for B in a.pool_B:
+        rng = random.Random(a.seed)
+        draws = [[rng.randint(1, 5) if t >= b % 8 else 0 for b in range(B)] for t in range(a.ticks)]
+        total = max(sum(d[b] for d in draws) for b in range(B))
+        x = synth_batch(B, total * int(enc.hop_length), 0, dev)
+        with torch.no_grad():
+            data = dec(enc(x), vq=True)[0] if a.decode else x
+            pos, padded, chunks = [0] * B, [], []
+            for hops in draws:
+                members = [b for b in range(B) if hops[b]]
+                xt = torch.zeros(len(members), data.shape[1], max(hops) * unit, device=dev)
+                for i, b in enumerate(members):
+                    xt[i, :, :hops[b] * unit] = data[b, :, pos[b]:pos[b] + hops[b] * unit]
+                padded.append((members, xt, [hops[b] for b in members]))
+                chunks.append([(b, data[b:b + 1, :, pos[b]:pos[b] + hops[b] * unit].contiguous()) for b in members])
+                pos = [p + h * unit for p, h in zip(pos, hops)]
+            pool = S.LookaheadPool(model, B)
+            singles = [stream_cls(model) for _ in range(B)]
+            emitted = {}
+
+            def run_pool():
+                sids, out = {}, 0
+                for members, xt, hops in padded:
+                    for b in members:
+                        if b not in sids:
+                            sids[b] = pool.open()
+                    out += sum(pool.push([sids[b] for b in members], xt, hops=hops)[1])
+                for s in sids.values():
+                    pool.close(s)
+                emitted["pool"] = out
+
+            def run_singles():
+                out = 0
+                for s in singles:
+                    s.reset()
+                for tick in chunks:
+                    for b, c in tick:
+                        out += singles[b].push(c).shape[-1]
+                emitted["singles"] = out
+
+            best = {}
+            for rep in range(a.reps + 1):
+                for name, leg in (("pool", run_pool), ("singles", run_singles)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    leg()
+                    torch.cuda.synchronize()
+                    dt = 1e3 * (time.perf_counter() - t0) / a.ticks
+                    if rep:  # the first round warms the weight caches, every window shape and sizes the state
+                        best[name] = min(best.get(name, dt), dt)
+            assert emitted["pool"] == emitted["singles"], emitted  # both arms handed out the same columns
+        print(json.dumps(dict(leg="lookahead_pool", model="default", precision=L.precision_name(),
+                              what="decode" if a.decode else "encode", B=B, ticks=a.ticks, seed=a.seed,
+                              pushes_per_tick=dict(pool=1.0, singles=round(sum(len(c) for c in chunks) / a.ticks, 2)),
+                              columns_out=emitted["pool"], ms_per_tick={k: round(v, 3) for k, v in best.items()},
+                              singles_over_pool=round(best["singles"] / best["pool"], 2),
+                              state_bytes_per_session=pool.state_bytes() // B)), flush=True)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--lookahead", action="store_true", help="LookaheadEncoder on the non-causal default model")
@@ -215,7 +293,7 @@ def main():
         from audiotokenization_amd import streaming as S
     dev = torch.device("cuda:0")
     if a.lookahead:
-        return lookahead_leg(a, dev)
+        return (lookahead_pool_leg if a.pool else lookahead_leg)(a, dev)
     enc, dec = build_model_pair("default", device=dev, causal=True)
     if a.pool:
         return (ragged_leg if a.ragged else pool_leg)(a, dev, enc, dec)
