@@ -31,6 +31,38 @@
 //   guaranteed (x6 latent 5.1e-4 off on one box).  sc1 loads bypass
 //   only the CU's L1; the XCD's L2 still serves its CUs.
 //   Every poll is bounded: on timeout the kernel counts it in *status and all workgroups leave.
+//
+// Software pipeline of the hand-off across half-steps (lstm_seq2_x6_kernel, a.pipe).
+//   Half-step n + 1 of a workgroup needs the OTHER half's flags at a value known in advance, so
+//   (1) wave 0 stores flag(n - 1) after the FIRST k-step of half-step n instead of after all of its MFMAs, behind a
+//       counted vmcnt that retires the publish stores (older) and leaves the ring's h loads issued in that k-step
+//       (younger, vmcnt retires in order) in flight;
+//   (2) every wave issues ONE non-blocking sc1 load of the flags half-step n + 1 will poll, beside the last ring loads
+//       of half-step n, and examines it after the MFMA loop;
+//   (3) a wave whose look showed every polled producer at the target issues the h loads of half-step n + 1's first
+//       HD - 1 k-steps into the (now free, loop-carried) register ring right there, behind a wavefront acquire fence,
+//       so they land behind the LDS reduction, the cell update and the publish; half-step n + 1 then starts at its
+//       MFMAs.  A wave whose look failed runs the blocking poll and the ring preamble at the top of n + 1 as before.
+//   (2) and (3) are compiled in only where the MFMA phase gives the flag time to arrive before the look (LOOK below:
+//   H = 1536, x6, 33-64 clips, where 99 % of the looks hit); in the shorter phases the look came too early, and a
+//   failed look costs more than the poll it was to replace.  (1) applies to every instantiation.
+//   Invariants:
+//   - the blocking polls stay where they were (top of a half-step), unchanged and bounded by spin_limit; the early
+//     look never blocks, spins or bails (one completed load, examined where the wave waits for its ring loads
+//     anyway);
+//   - a workgroup's flag store for half-step k precedes, in program order, its blocking poll of any half-step that
+//     transitively needs it: flag(n - 1) was stored before poll(n + 1) and now sits one MFMA phase earlier still
+//     (behind poll(n) or the successful look that replaced it, both of which need flags of half-steps <= n - 2 only);
+//   - every load of handed-off bytes is an sc1 load issued after a COMPLETED flag load of the same wave showed the
+//     producer's flag (the blocking poll or the early look), with the wavefront acquire fence between them;
+//   - the flag store comes after a wait that retires every publish store of the one storing wave (the counted wait,
+//     or vmcnt(0) where no MFMA phase ran);
+//   - on bail the workgroups leave with loads outstanding (prefetched ring slots included), as they already could;
+//   - with h0 (sh = 1) the poll of t = 0 exists; half 1's is covered by the look in half-step 0 like any other, half
+//     0's has no earlier half-step and blocks; T = 1 without h0 publishes, looks at and polls nothing;
+//   - a.pipe = 0 (BC_LSTM_SEQ_PIPE=0, bc_debug_set_lstm_pipeline) is uniform per launch and restores the old schedule:
+//     flag after the MFMA loop behind vmcnt(0), no look, no prefetch.  Same products summed in the same order either
+//     way: outputs are bit-identical.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -54,6 +86,10 @@ constexpr int LS_U = 8;          // hidden units per workgroup
 constexpr int LS_WAVES = 4;
 constexpr int LS_NB = 64;        // clips per launch (4 n-tiles of 16)
 constexpr int LS_HD = 4;         // lstm_seq2: depth of the h_{t-1} register ring (k-steps)
+constexpr int LS_HD_X6 = 3;      // ... of x6 halves of 32 clips (KS = 12: W_hh holds 288 of the 512 registers; 24 MFMAs per
+                                 // k-step cover the latency at depth 3, depth 4 measured 2 % slower)
+constexpr int LS_FS_KS = 0;      // lstm_seq2 pipeline: the k-step that carries the deferred flag store
+constexpr int LS_EL_OFF = 0;     // lstm_seq2 pipeline: the early look goes out at k-step KS - HD + LS_EL_OFF
 constexpr int LS_HSTEP_PER_UNIT = LS_NB * 3 / 2;  // floats of hseq per hidden unit per step (3 bf16 planes)
 constexpr int LS_SC1 = 16;       // buffer-op cache policy: sc1 (write-through / L1 bypass)
 constexpr unsigned LS_SPIN_LIMIT = 1u << 22;
@@ -81,9 +117,11 @@ struct LstmSeqArgs {
   // lens [Btot] (lstm_seq2 only; a session pool's push with a chunk length per clip) or nullptr: clip b's hT / cT
   // are its state after step clamp(lens[b], 1, T) - 1 instead of the last step; y is all T steps either way
   const int* lens;
+  int pipe;  // lstm_seq2 only: 1 = pipelined hand-off (early flag store, early look, tail prefetch), 0 = the old schedule
 };
 
 constexpr int LS_STAMP_T = 2048;  // steps recorded per stamped workgroup
+constexpr int LS_STAMP_EV = 16;   // lstm_seq2: events per (half-step, wave) row (lstm_seq_x6_kernel keeps 8)
 
 template <int P> struct LsFrag { typedef __bf16 type __attribute__((ext_vector_type(8))); };
 template <> struct LsFrag<2> { typedef _Float16 type __attribute__((ext_vector_type(8))); };
@@ -125,10 +163,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t ls_rsrc(const void* p, unsigne
 }
 
 // 16-byte sc1 load of a handed-off h_t fragment (L1 bypass: see the hand-off notes at the top)
+// (soff: a wave-uniform part of the offset, kept in a scalar register)
 template <typename T>
-__device__ __forceinline__ T ls_load_sc1(__amdgpu_buffer_rsrc_t r, unsigned off) {
+__device__ __forceinline__ T ls_load_sc1(__amdgpu_buffer_rsrc_t r, unsigned off, unsigned soff = 0) {
   static_assert(sizeof(T) == 16, "16-byte fragments");
-  return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, LS_SC1));
+  return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, off, soff, LS_SC1));
 }
 
 template <int KS>
@@ -352,8 +391,11 @@ __global__ void __launch_bounds__(256, 1) lstm_seq_x6_kernel(LstmSeqArgs a) {
 // clips (BASELINE config 5 runs 32 per GPU), where halves of 32 left half 1 empty -- every step still paid its
 // poll / load / reduction / publish chain for no clips.  Same hseq layout (n-tile 1 unused), same per-cell
 // arithmetic in the same order: a clip's outputs do not depend on NTH (test_reslstm_half_split_bit_identical).
-template <int KS, int P, int NTH = 2>
-__global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
+// STAMPS: the diagnostic timeline (BC_LSTM_SEQ_STAMPS) is compiled into a kernel of its own
+// (lstm_seq2_x6_stamped_kernel): at KS = 12, P = 3 the stamps' stores and branches cost the register allocator
+// some 60 VGPRs it does not have, and the product kernel carries none of them.
+template <int KS, int P, int NTH, bool STAMPS>
+__device__ __forceinline__ void lstm_seq2_body(const LstmSeqArgs& a) {
   typedef typename LsFrag<P>::type frag_t;
   static_assert(NTH == 1 || NTH == 2, "halves of 16 or 32 clips");
   constexpr int NH = 16 * NTH;                 // clips per half
@@ -361,6 +403,7 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
   __shared__ float hs[NH][LS_U + 1];           // one half's h_t gathered per clip
   __shared__ int tls[2 * NH];                  // a.lens of the launch's clips (read only when a.lens is given)
   __shared__ int bail;
+  __shared__ unsigned sv[LS_WAVES][12];        // STAMPS: a half-step's events per wave (unused, and dropped, otherwise)
 
   const int g = blockIdx.x;
   const int G = gridDim.x;
@@ -457,16 +500,58 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
   int pend_h = -1;        // wave 0: half whose h stores are issued but whose flag is not yet set
   unsigned pend_v = 0;
 
+  // h_{t-1} fragments through a register ring LS_HD k-steps deep: the loads of k-step ks + LS_HD - 1
+  // are issued before k-step ks's MFMAs, so L2 latency hides behind LS_HD - 1 k-steps of MFMAs
+  // (depth 2 left ~2300 of a half-step's 4600 load+MFMA cycles exposed, profiles/r01g_lstm_h3_stamps.txt).
+  // Loop-carried: under a.pipe the tail of a half-step fills slots 0 .. HD - 2 for the next one (pre).
+  constexpr int HD0 = P == 3 && NTH == 2 ? LS_HD_X6 : LS_HD;
+  constexpr int HD = HD0 < KS ? HD0 : KS;
+  // the early look and the tail prefetch: only where >= 192 MFMAs lie between the flag store (k-step 0) and the look
+  constexpr bool LOOK = (KS - HD) * NTH * 2 * (P == 3 ? 6 : 3) >= 192;
+  constexpr int FS_KS = LS_FS_KS < KS ? LS_FS_KS : KS - 1;          // a.pipe: the k-step after whose MFMAs wave 0 stores the deferred flag
+  constexpr int EL_KS = KS - HD + LS_EL_OFF < KS ? KS - HD + LS_EL_OFF : KS - 1;  // a.pipe: the k-step that issues the early look
+  // ring loads certainly younger than the publish stores at the flag store: those issued inside k-steps 0 .. FS_KS
+  // (the preamble's are older when they were prefetched; gx / y / state accesses are conditional: not counted)
+  constexpr int FS_YOUNGER = ((FS_KS < KS - HD ? FS_KS : KS - HD) + 1) * NTH * P;
+  static_assert(FS_YOUNGER >= 0 && FS_YOUNGER < 64, "vmcnt immediate");
+  frag_t hbuf[HD][2][P];
+  bool pre = false;  // wave-uniform: ring slots 0 .. HD - 2 hold this half-step's first k-steps (prefetched in the last tail)
+  // this wave's K range of one half's hseq slot: k-steps w * KS .. w * KS + KS - 1, 2 * P KB each
+  auto h_rsrc = [&](long long slot, int half) {
+    return ls_rsrc(a.hseq + (slot * 2 + half) * hhalf + (long long)w * (KS * 2 * P * 256), (unsigned)(KS * 2 * P * 1024));
+  };
+  // (the lane's 16 bytes are the only vector part of the address; the fragment's place is a compile-time scalar offset)
+  auto load_ks = [&](const __amdgpu_buffer_rsrc_t hr, int ks, frag_t (&dst)[2][P]) {
+#pragma unroll
+    for (int nt = 0; nt < NTH; ++nt)
+#pragma unroll
+      for (int p = 0; p < P; ++p) {
+        const int f = (ks * 2 + nt) * P + p;  // fragment f at f KB: 4 KB groups by scalar offset, the rest an immediate
+        dst[nt][p] = ls_load_sc1<frag_t>(hr, (unsigned)(lane * 16 + (f & 3) * 1024), (unsigned)((f >> 2) * 4096));
+      }
+  };
+
   long long* stamp_row = nullptr;
-  if (a.stamps && lane == 0 && (g == 0 || g == G / 2)) stamp_row = a.stamps + (long long)(g == 0 ? 0 : 1) * LS_STAMP_T * 32;
+  if constexpr (STAMPS)
+    if (a.stamps && lane == 0 && (g == 0 || g == G / 2))
+      stamp_row = a.stamps + (long long)(g == 0 ? 0 : 1) * LS_STAMP_T * 4 * LS_STAMP_EV;
 
   for (int t = 0; t < a.T; ++t) {
 #pragma unroll 1
     for (int h = 0; h < 2; ++h) {
       const int ts = 2 * t + h;  // stamp row
+      // events: 0 start, 1 poll done (or skipped), 2 MFMAs done, 3 reduction barrier passed, 4 cell done, 5 gather
+      // barrier passed, 6 publish done; a.pipe: 7 early look issued, 8 look examined, 9 prefetch issued after
+      // the look (0: it failed), 11 1 = the blocking poll ran.
+      // Taken without a branch (ticks since event 0 into the wave's LDS row, every lane the same word), written out
+      // once with event 6: a global store or a branch at each site moves the schedule the timeline is there to show.
+      long long st0 = 0;
+      if constexpr (STAMPS) {
+        st0 = (long long)__builtin_amdgcn_s_memtime();
+        if (lane < 12) sv[w][lane] = 0;
+      }
 #define LS2_STAMP(ev) \
-  if (stamp_row && ts < LS_STAMP_T) stamp_row[(ts * 4 + w) * 8 + (ev)] = (long long)__builtin_amdgcn_s_memtime();
-      LS2_STAMP(0)
+  if constexpr (STAMPS) sv[w][ev] = (unsigned)__builtin_amdgcn_s_memtime() - (unsigned)st0 + 1u;
       const int clip = h * NH + cbh;
       const bool ok = cell && clip < a.nb;
       float gxv[4];
@@ -480,47 +565,53 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) acc[mt][nt] = floatx4{0.f, 0.f, 0.f, 0.f};
 
+      // the next half-step (other half), the flag value it needs and the hseq slot it reads
+      const int hn = h ^ 1, tn = t + h;
+      const unsigned tgt_n = (unsigned)(tn + sh);
+      bool look = false;  // an early look at the next half-step's flags is in flight / was taken (a.pipe)
+      unsigned fe = 0;
+      const ls_gu32* fln = flags + hn * 256 + w * nprod;
+
       if (t + sh > 0) {
-        const ls_gu32* fl = flags + h * 256 + w * nprod;
-        unsigned spins = 0;
-        while (!BC_ABL(a.dbg, 4)) {
-          const unsigned f = lane < nprod ? __hip_atomic_load(fl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                          : 0xffffffffu;
-          if (__all(f >= (unsigned)(t + sh))) break;
-          if (++spins > a.spin_limit) {
-            if (lane == 0) {
-              atomicAdd(a.status, 1);
-              atomicAdd(a.status_total, 1);
-              bail = 1;
-            }
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-        // compiler ordering only (keeps the loads below the poll); visibility comes from the sc1 loads
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        LS2_STAMP(1)
         // h_{t-1} of this half: sc1 loads (the hand-off form at the top of the file)
-        const __amdgpu_buffer_rsrc_t hr = ls_rsrc(a.hseq + ((long long)(t - 1 + sh) * 2 + h) * hhalf,
-                                                  (unsigned)(hhalf * 4));
-        // h_{t-1} fragments through a register ring LS_HD k-steps deep: the loads of k-step ks + LS_HD - 1
-        // are issued before k-step ks's MFMAs, so L2 latency hides behind LS_HD - 1 k-steps of MFMAs
-        // (depth 2 left ~2300 of a half-step's 4600 load+MFMA cycles exposed, profiles/r01g_lstm_h3_stamps.txt)
-        constexpr int HD = LS_HD < KS ? LS_HD : KS;
-        frag_t hbuf[HD][2][P];
-        auto load_ks = [&](int ks, frag_t (&dst)[2][P]) {
-          const int ksa = w * KS + ks;
+        const __amdgpu_buffer_rsrc_t hr = h_rsrc(t - 1 + sh, h);
+        if (!pre) {
+          const ls_gu32* fl = flags + h * 256 + w * nprod;
+          unsigned spins = 0;
+          while (!BC_ABL(a.dbg, 4)) {
+            const unsigned f = lane < nprod ? __hip_atomic_load(fl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                            : 0xffffffffu;
+            if (__all(f >= (unsigned)(t + sh))) break;
+            if (++spins > a.spin_limit) {
+              if (lane == 0) {
+                atomicAdd(a.status, 1);
+                atomicAdd(a.status_total, 1);
+                bail = 1;
+              }
+              break;
+            }
+            __builtin_amdgcn_s_sleep(1);
+          }
+          // compiler ordering only (keeps the loads below the poll); visibility comes from the sc1 loads
+          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          LS2_STAMP(1)
+          if constexpr (STAMPS) sv[w][11] = 1;
 #pragma unroll
-          for (int nt = 0; nt < NTH; ++nt)
-#pragma unroll
-            for (int p = 0; p < P; ++p)
-              dst[nt][p] = ls_load_sc1<frag_t>(hr, (unsigned)((((ksa * 2 + nt) * P + p) * 64 + lane) * 16));
-        };
-#pragma unroll
-        for (int ks = 0; ks + 1 < HD; ++ks) load_ks(ks, hbuf[ks]);
+          for (int ks = 0; ks + 1 < HD; ++ks) load_ks(hr, ks, hbuf[ks]);
+        } else {
+          LS2_STAMP(1)
+        }
+        pre = false;
+        if constexpr (LOOK) look = a.pipe && tn < a.T;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          if (ks + HD - 1 < KS) load_ks(ks + HD - 1, hbuf[(ks + HD - 1) % HD]);
+          if (ks + HD - 1 < KS) load_ks(hr, ks + HD - 1, hbuf[(ks + HD - 1) % HD]);
+          if (ks == EL_KS && look) {
+            // the early look: one relaxed agent-scope (sc1) load per polled producer, behind the ring loads just
+            // issued (vmcnt retires in order: waiting for it costs nothing the last k-step does not wait for anyway)
+            fe = __hip_atomic_load(fln + (lane < nprod ? lane : 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            LS2_STAMP(7)
+          }
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
           for (int nt = 0; nt < NTH; ++nt) {
@@ -545,15 +636,46 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
               }
             }
           }
+          if (ks == FS_KS) {
+            // a.pipe: the deferred flag of the previous half-step's publish, one MFMA phase early.  The counted wait
+            // retires the publish stores and everything older; the FS_YOUNGER ring loads issued since stay in flight
+            __builtin_amdgcn_sched_barrier(0);
+            if (a.pipe && w == 0 && pend_h >= 0) {
+              asm volatile("s_waitcnt vmcnt(%0)" ::"n"(FS_YOUNGER) : "memory");
+              if (lane == 0) __hip_atomic_store(flags + pend_h * 256 + g, pend_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              pend_h = -1;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
         }
       }
       LS2_STAMP(2)
-      // deferred flag of the previous half-step's publish: its stores were issued a whole
-      // half-step ago, so this drain is (nearly) free
+      // deferred flag of the previous half-step's publish where it is still pending (a.pipe = 0, or no MFMA phase ran:
+      // t = 0 without h0): its stores were issued a whole half-step ago, so this drain is (nearly) free
       if (w == 0 && pend_h >= 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(flags + pend_h * 256 + g, pend_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         pend_h = -1;
+      }
+
+      // the ring is free: where the look shows every polled producer at the target, the next half-step's first
+      // k-steps go out now and land behind the reduction, the cell update and the publish
+      auto prefetch_next = [&]() {  // (look only: t + sh > 0 and tn < T, so slot tn - 1 + sh is one of 0 .. T - 2 + sh)
+        const __amdgpu_buffer_rsrc_t hrn = h_rsrc(tn - 1 + sh, hn);
+        // compiler ordering only, as behind the blocking poll: the sc1 loads follow the completed flag load
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int ks = 0; ks + 1 < HD; ++ks) load_ks(hrn, ks, hbuf[ks]);
+        pre = true;
+      };
+      if (look) {
+        const bool hit = __all(fe >= tgt_n);
+        LS2_STAMP(8)
+        if (hit) {
+          prefetch_next();
+          LS2_STAMP(9)
+        }
+        __builtin_amdgcn_sched_barrier(0);
       }
 
 #pragma unroll
@@ -592,7 +714,16 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
         pend_h = h;
         pend_v = (unsigned)(t + 1 + sh);
       }
-      LS2_STAMP(6)
+      if constexpr (STAMPS)
+        if (stamp_row && ts < LS_STAMP_T) {
+          long long* sr = stamp_row + (ts * 4 + w) * LS_STAMP_EV;
+          sr[0] = st0;
+          sr[6] = (long long)__builtin_amdgcn_s_memtime();
+#pragma unroll
+          for (int ev = 1; ev < 11; ++ev)
+            if (ev != 6) sr[ev] = sv[w][ev] ? st0 + (sv[w][ev] - 1u) : 0;
+          sr[11] = sv[w][11];
+        }
       if (ok) {
         const long long yi = (long long)(g * LS_U + cu) * TB + (long long)t * a.Btot + a.b0 + clip;
         if (BC_DOK(yi < (long long)a.H * TB)) a.y[yi] = hq;
@@ -605,6 +736,16 @@ __global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
     }
   }
   // no flag can still be pending: the last step publishes nothing
+}
+
+template <int KS, int P, int NTH = 2>
+__global__ void __launch_bounds__(256, 1) lstm_seq2_x6_kernel(LstmSeqArgs a) {
+  lstm_seq2_body<KS, P, NTH, false>(a);
+}
+
+template <int KS, int P, int NTH = 2>
+__global__ void __launch_bounds__(256, 1) lstm_seq2_x6_stamped_kernel(LstmSeqArgs a) {
+  lstm_seq2_body<KS, P, NTH, true>(a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -717,13 +858,20 @@ static long long* lstm_seq_stamp_buffer() {
   static long long* p = [] {
     const char* e = getenv("BC_LSTM_SEQ_STAMPS");
     long long* q = nullptr;
-    if (e && atoi(e) && hipMalloc(&q, sizeof(long long) * 2 * LS_STAMP_T * 32) != hipSuccess) q = nullptr;
+    if (e && atoi(e) && hipMalloc(&q, sizeof(long long) * 2 * LS_STAMP_T * 4 * LS_STAMP_EV) != hipSuccess) q = nullptr;
     return q;
   }();
   return p;
 }
 
 static unsigned g_spin_limit = LS_SPIN_LIMIT;
+
+// lstm_seq2's pipelined hand-off (the header's "Software pipeline"): BC_LSTM_SEQ_PIPE=0 or
+// bc_debug_set_lstm_pipeline(0) restores the old schedule (A/B timing, the bit-identity test)
+static int g_lstm_pipe = [] {
+  const char* e = getenv("BC_LSTM_SEQ_PIPE");
+  return e && atoi(e) == 0 ? 0 : 1;
+}();
 
 static int device_cus() {
   static int n = [] {
@@ -744,11 +892,15 @@ static bool all_resident(K kernel, int G) {
   return per_cu >= 1 && (long long)G <= (long long)per_cu * device_cus();
 }
 
-static bool seq_resident(int KS, int planes, bool halves, int G) {
+static bool seq_resident(int KS, int planes, bool halves, bool stamped, int G) {
 #define BC_LS_RES(K)                                                                        \
   case K:                                                                                   \
+    if (planes == 2 && stamped)                                                             \
+      return all_resident(lstm_seq2_x6_stamped_kernel<K, 2>, G) && all_resident(lstm_seq2_x6_stamped_kernel<K, 2, 1>, G); \
     if (planes == 2)                                                                        \
       return all_resident(lstm_seq2_x6_kernel<K, 2>, G) && all_resident(lstm_seq2_x6_kernel<K, 2, 1>, G); \
+    if (halves && stamped)                                                                  \
+      return all_resident(lstm_seq2_x6_stamped_kernel<K, 3>, G) && all_resident(lstm_seq2_x6_stamped_kernel<K, 3, 1>, G); \
     if (halves) return all_resident(lstm_seq2_x6_kernel<K, 3>, G) && all_resident(lstm_seq2_x6_kernel<K, 3, 1>, G); \
     return all_resident(lstm_seq_x6_kernel<K>, G);
   switch (KS) {
@@ -793,6 +945,7 @@ int lstm_seq_launch(const float* gx, const unsigned short* whh, float* y, void* 
   a.hT = hT;
   a.cT = cT;
   a.lens = lens;
+  a.pipe = g_lstm_pipe;
   // BC_LSTM_SEQ_HALVES=1: the single-batch kernel (kept for A/B timing), else two interleaved halves
   static const bool halves = [] {
     const char* e = getenv("BC_LSTM_SEQ_HALVES");
@@ -802,7 +955,8 @@ int lstm_seq_launch(const float* gx, const unsigned short* whh, float* y, void* 
   static int resident_checked[4][2] = {};  // per (H/128 case, kernel): 1 ok, -1 refused
   const int ks_idx = H == 256 ? 0 : H == 512 ? 1 : H == 1024 ? 2 : 3;
   int& rs = resident_checked[ks_idx][planes == 2 ? 0 : 1];
-  if (rs == 0) rs = seq_resident(H / 128, planes, halves, G) ? 1 : -1;
+  const bool stamped = a.stamps != nullptr;  // (fixed per process: BC_LSTM_SEQ_STAMPS is read once)
+  if (rs == 0) rs = seq_resident(H / 128, planes, halves, stamped, G) ? 1 : -1;
   if (rs < 0) return BC_ERR_UNSUPPORTED;
   // BC_LSTM_NH16=0 keeps launches of <= 32 clips on halves of 32 (A/B timing)
   static const bool nh16 = [] {
@@ -816,7 +970,16 @@ int lstm_seq_launch(const float* gx, const unsigned short* whh, float* y, void* 
     if (hipMemsetAsync(a.flags, 0, LS_FLAG_BYTES, st) != hipSuccess) return BC_ERR_LAUNCH;
 #define BC_LS_CASE(KS)                                                                      \
   case KS:                                                                                  \
-    if (planes == 2 && h16)                                                                 \
+    if (stamped && (planes == 2 || halves)) {                                               \
+      if (planes == 2 && h16)                                                               \
+        hipLaunchKernelGGL((lstm_seq2_x6_stamped_kernel<KS, 2, 1>), dim3(G), dim3(256), 0, st, a); \
+      else if (planes == 2)                                                                 \
+        hipLaunchKernelGGL((lstm_seq2_x6_stamped_kernel<KS, 2>), dim3(G), dim3(256), 0, st, a);    \
+      else if (h16)                                                                         \
+        hipLaunchKernelGGL((lstm_seq2_x6_stamped_kernel<KS, 3, 1>), dim3(G), dim3(256), 0, st, a); \
+      else                                                                                  \
+        hipLaunchKernelGGL((lstm_seq2_x6_stamped_kernel<KS, 3>), dim3(G), dim3(256), 0, st, a);    \
+    } else if (planes == 2 && h16)                                                          \
       hipLaunchKernelGGL((lstm_seq2_x6_kernel<KS, 2, 1>), dim3(G), dim3(256), 0, st, a);    \
     else if (planes == 2)                                                                   \
       hipLaunchKernelGGL((lstm_seq2_x6_kernel<KS, 2>), dim3(G), dim3(256), 0, st, a);       \
@@ -866,11 +1029,20 @@ extern "C" int bc_debug_set_lstm_spin_limit(long long limit) {
   return 0;
 }
 
+// Diagnostics only (not part of include/bigcodec.h): the pipelined hand-off of lstm_seq2 on (nonzero) or off (0);
+// returns the previous value.
+extern "C" int bc_debug_set_lstm_pipeline(int on) {
+  const int old = bc::g_lstm_pipe;
+  bc::g_lstm_pipe = on ? 1 : 0;
+  return old;
+}
+
 // Diagnostics only (not part of include/bigcodec.h): copy the last persistent launch's stamps
-// [2 workgroups][2048 steps][4 waves][8 events] (s_memtime ticks) to the host; synchronises.
+// [2 workgroups][2048 half-steps][4 waves][16 events] (lstm_seq_x6_kernel: [2][2048 steps][4][8] at the front;
+// s_memtime ticks) to the host; synchronises.
 extern "C" int bc_debug_lstm_stamps(long long* host, long long n) {
   long long* p = bc::lstm_seq_stamp_buffer();
-  if (!p || !host || n <= 0 || n > 2LL * bc::LS_STAMP_T * 32) return 1;
+  if (!p || !host || n <= 0 || n > 2LL * bc::LS_STAMP_T * 4 * bc::LS_STAMP_EV) return 1;
   return hipMemcpy(host, p, sizeof(long long) * n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : 2;
 }
 

@@ -56,22 +56,26 @@ def main():
 
 def timeline(T):
     """Per-step phase durations (s_memtime ticks) of workgroups 0 and G/2 from the last launch:
-    0 step start, 1 poll done, 2 MFMAs done, 3 reduction barrier passed, 4 cell done,
-    5 gather barrier passed, 6 publish done (wave 0)."""
+    0 step start, 1 poll done (or skipped), 2 MFMAs done, 3 reduction barrier passed, 4 cell done,
+    5 gather barrier passed, 6 publish done (wave 0).  The two-half kernel (rows of 16 events) adds the
+    pipelined hand-off's: 7 early look issued, 8 look examined, 9 prefetch issued after the look (0: it
+    failed), 11 1 = the blocking poll ran."""
     import ctypes as C
 
     lib = L.load()
-    n = 2 * 2048 * 32
+    halves = os.environ.get("BC_LSTM_SEQ_HALVES", "2") != "1"
+    nev = 16 if halves else 8
+    n = 2 * 2048 * 4 * nev
     buf = (C.c_longlong * n)()
     fn = lib.bc_debug_lstm_stamps
     fn.argtypes = [C.c_void_p, C.c_longlong]
     if fn(C.addressof(buf), n) != 0:
         print("no stamps")
         return
-    if os.environ.get("BC_LSTM_SEQ_HALVES", "2") != "1":
+    if halves:
         T = min(2048, 2 * T)  # rows are half-steps (2t + half)
         print("rows = half-steps")
-    s = np.frombuffer(buf, dtype=np.int64).reshape(2, 2048, 4, 8)[:, :T]
+    s = np.frombuffer(buf, dtype=np.int64).reshape(2, 2048, 4, nev)[:, :T]
     names = ["poll", "load+mfma", "red.barrier", "cell", "gather.barrier", "publish", "tail->next"]
     lo, hi = 10, T - 10
     for wgi in range(2):
@@ -81,6 +85,19 @@ def timeline(T):
             d = [np.median(s[wgi, lo:hi, w, k + 1] - s[wgi, lo:hi, w, k]) for k in range(6)]
             d.append(np.median(s[wgi, lo + 1:hi + 1, w, 0] - s[wgi, lo:hi, w, 6]))
             print(f"  wave {w}: " + "  ".join(f"{nm} {v:6.0f}" for nm, v in zip(names, d)))
+            if not halves:
+                continue
+            r = s[wgi, lo:hi, w]
+            looked = r[:, 7] != 0
+            if not looked.any():
+                print("          pipeline off: no early look")
+                continue
+            hit, polled = r[:, 9] != 0, r[:, 11] != 0
+            med = lambda v: float(np.median(v)) if v.size else float("nan")  # noqa: E731
+            print(f"          look issued at +{med((r[:, 7] - r[:, 0])[looked]):.0f}, examined at "
+                  f"+{med((r[:, 8] - r[:, 0])[looked]):.0f}; hit {100 * hit.mean():.1f} % (prefetch at "
+                  f"+{med((r[:, 9] - r[:, 0])[hit]):.0f}); blocking poll ran in {100 * polled.mean():.1f} % "
+                  f"of half-steps, {med((r[:, 1] - r[:, 0])[polled]):.0f} ticks when it did")
 
 
 if __name__ == "__main__":
