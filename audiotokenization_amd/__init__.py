@@ -7,6 +7,7 @@ reference's own module interface.
 from . import _lib  # noqa: F401
 from .codec import BigCodecDecoder, BigCodecEncoder
 from .config import AttrDict, load_config, preset
+from .conformer import ConformerDecoderISTFT, ConformerEncoderSTFT
 from .lightning_shim import CodecLightningModule
 from .blocks import DecoderBlock, EncoderBlock, ResidualUnit, ResLSTM
 from .conv import WNConv1d, WNConvTranspose1d
@@ -14,7 +15,7 @@ from .modules import Activation1d, FactorizedVectorQuantize, ResidualVQ, SnakeBe
 from .streaming import LookaheadPool
 
 __all__ = [
-    "LookaheadPool",
+    "LookaheadPool", "ConformerEncoderSTFT", "ConformerDecoderISTFT",
     "BigCodecEncoder", "BigCodecDecoder", "CodecLightningModule", "AttrDict", "load_config", "preset",
     "Activation1d", "DecoderBlock", "EncoderBlock", "FactorizedVectorQuantize", "ResidualUnit", "ResidualVQ",
     "ResLSTM", "SnakeBeta",

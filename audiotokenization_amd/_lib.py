@@ -83,6 +83,13 @@ _SIGS = {
     "bc_code_hist": (I, [P, I, P, P, I, L, I, P]),
     "bc_stoi_workspace_bytes": (L, [I, L, I, I]),
     "bc_stoi": (I, [P, P, P, P, I, I, I, P, P, P, P, I, L, P]),
+    "bc_stft_frames": (I, [P, P, P, I, L, I, I, I, P]),
+    "bc_rmsnorm_fwd": (I, [P, P, P, I, I, I, C.c_float, I, P]),
+    "bc_dwconv_glu_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
+    "bc_swiglu_fwd": (I, [P, P, I, I, L, P]),
+    "bc_attention_tiles": (I, [P, P]),
+    "bc_attention_fwd": (I, [P, P, P, I, I, I, I, I, P]),
+    "bc_istft_head": (I, [P, P, P, P, I, I, I, I, P]),
     "bc_flac_info": (I, [P, L, P, P, P, P]),
     "bc_flac_decode": (L, [P, L, P, I, L, I]),
     "bc_conv1d_kernel_name": (I, [I, I, I, I, C.c_char_p, I]),

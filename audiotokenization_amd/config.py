@@ -52,17 +52,49 @@ DECODER_KEYS = ("in_channels", "upsample_initial_channel", "ngf", "use_rnn", "rn
                 "codebook_dim")
 
 
+# lightning_module.py:102-116 / 141-163 (the conformer decoder does forward vq_weight_init)
+CONFORMER_ENCODER_KEYS = ("hop_length", "n_fft", "window_size", "dim", "n_layers", "n_head", "ffn_mult",
+                          "conv_kernel_size", "dropout", "max_seq_len", "rope_theta", "causal", "out_channels")
+CONFORMER_DECODER_KEYS = ("in_channels", "hop_length", "n_fft", "window_size", "dim", "n_layers", "n_head", "ffn_mult",
+                          "conv_kernel_size", "dropout", "max_seq_len", "rope_theta", "causal", "fsq", "fsq_levels",
+                          "vq_num_quantizers", "vq_commit_weight", "vq_weight_init", "vq_full_commit_loss",
+                          "codebook_size", "codebook_dim")
+
+
+def encoder_type(enccfg: Mapping) -> str:
+    """'bigcodec' or 'conformer_stft' (lightning_module.py:89, 101); anything else is the reference's ValueError."""
+    t = enccfg.get("type", "bigcodec")
+    if t not in ("bigcodec", "conformer_stft"):
+        raise ValueError(f"Invalid codec encoder type: {t}")
+    return t
+
+
+def decoder_type(deccfg: Mapping) -> str:
+    """'bigcodec' or 'conformer_istft' (lightning_module.py:120, 140)."""
+    t = deccfg.get("type", "bigcodec")
+    if t not in ("bigcodec", "conformer_istft"):
+        raise ValueError(f"Invalid codec decoder type: {t}")
+    return t
+
+
+def is_conformer(cfg) -> bool:
+    """Whether cfg.model selects the Conformer-STFT family on either side."""
+    m = cfg["model"]
+    return encoder_type(m["codec_encoder"]) != "bigcodec" or decoder_type(m["codec_decoder"]) != "bigcodec"
+
+
 def encoder_kwargs(enccfg: Mapping) -> dict:
-    """lightning_module.py:89-99."""
-    if enccfg.get("type", "bigcodec") != "bigcodec":
-        raise NotImplementedError(f"codec encoder type {enccfg.get('type')!r} is out of scope (BigCodec only)")
+    """lightning_module.py:89-99 (bigcodec) / 102-116 (conformer_stft)."""
+    if encoder_type(enccfg) == "conformer_stft":
+        return {k: enccfg[k] for k in CONFORMER_ENCODER_KEYS}
     return {k: enccfg[k] for k in ENCODER_KEYS}
 
 
 def decoder_kwargs(deccfg: Mapping) -> dict:
-    """lightning_module.py:124-139 (note: the reference does not forward vq_weight_init)."""
-    if deccfg.get("type", "bigcodec") != "bigcodec":
-        raise NotImplementedError(f"codec decoder type {deccfg.get('type')!r} is out of scope (BigCodec only)")
+    """lightning_module.py:124-139 (bigcodec; the reference does not forward vq_weight_init there) / 141-163
+    (conformer_istft)."""
+    if decoder_type(deccfg) == "conformer_istft":
+        return {k: deccfg[k] for k in CONFORMER_DECODER_KEYS}
     return {k: deccfg[k] for k in DECODER_KEYS}
 
 
@@ -100,6 +132,28 @@ PRESETS = {
                               causal=False, antialias=False, vq_num_quantizers=1, vq_commit_weight=0.25,
                               vq_weight_init=False, vq_full_commit_loss=False, fsq=False, fsq_levels=[4, 4, 4, 8],
                               codebook_size=8192, codebook_dim=8),
+    },
+    # config1/model/base.yaml:1-58 (the Conformer-STFT family, 3.5 M parameters per side)
+    "conformer": {
+        "codec_encoder": dict(type="conformer_stft", hop_length=200, n_fft=800, window_size=800, dim=256, n_layers=6,
+                              n_head=8, ffn_mult=4, conv_kernel_size=31, dropout=0.1, max_seq_len=8192, rope_theta=500,
+                              causal=False, out_channels=256),
+        "codec_decoder": dict(type="conformer_istft", in_channels=256, hop_length=200, n_fft=800, window_size=800,
+                              dim=256, n_layers=6, n_head=8, ffn_mult=4, conv_kernel_size=31, dropout=0.1,
+                              max_seq_len=8192, rope_theta=500, causal=False, vq_num_quantizers=1,
+                              vq_commit_weight=0.25, vq_weight_init=False, fsq=False, fsq_levels=[4, 4, 4, 4, 4, 8],
+                              vq_full_commit_loss=False, codebook_size=8192, codebook_dim=8),
+    },
+    # a two-layer model of the same family for the tests (no reference file), head_dim 32 like config1's
+    "conformer_debug": {
+        "codec_encoder": dict(type="conformer_stft", hop_length=200, n_fft=800, window_size=800, dim=64, n_layers=2,
+                              n_head=2, ffn_mult=4, conv_kernel_size=31, dropout=0.1, max_seq_len=8192, rope_theta=500,
+                              causal=False, out_channels=64),
+        "codec_decoder": dict(type="conformer_istft", in_channels=64, hop_length=200, n_fft=800, window_size=800,
+                              dim=64, n_layers=2, n_head=2, ffn_mult=4, conv_kernel_size=31, dropout=0.1,
+                              max_seq_len=8192, rope_theta=500, causal=False, vq_num_quantizers=1,
+                              vq_commit_weight=0.25, vq_weight_init=False, fsq=False, fsq_levels=[4, 4, 4, 8],
+                              vq_full_commit_loss=False, codebook_size=8192, codebook_dim=8),
     },
 }
 

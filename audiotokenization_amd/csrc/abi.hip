@@ -824,6 +824,7 @@ int bc_dbg_fetch_lstm_seq(unsigned*);
 int bc_dbg_fetch_elementwise(unsigned*);
 int bc_dbg_fetch_metrics(unsigned*);
 int bc_dbg_fetch_stoi(unsigned*);
+int bc_dbg_fetch_conformer(unsigned*);
 int bc_debug_status(unsigned* out) {
   if (!out) return BC_ERR_ARG;
   if (hipDeviceSynchronize() != hipSuccess) return BC_ERR_LAUNCH;
@@ -832,7 +833,7 @@ int bc_debug_status(unsigned* out) {
                                      bc_dbg_fetch_conv1d_x6_p3, bc_dbg_fetch_resunit_x6, bc_dbg_fetch_resunit_w16,
                                      bc_dbg_fetch_resunit_rr,
                                      bc_dbg_fetch_pw_presplit, bc_dbg_fetch_lstm_seq, bc_dbg_fetch_elementwise, bc_dbg_fetch_metrics,
-                                     bc_dbg_fetch_stoi,
+                                     bc_dbg_fetch_stoi, bc_dbg_fetch_conformer,
                                      bc_dbg_fetch_abi};
   for (auto f : fetch)
     if (f(out)) return BC_ERR_LAUNCH;

@@ -755,6 +755,99 @@ void code_hist_(const Tensor& counts, const Tensor& codes, const optional<Tensor
      "bc_code_hist");
 }
 
+// ---- Conformer-STFT family (csrc/conformer.hip) --------------------------------------------------------------
+Tensor stft_frames(const Tensor& x, const Tensor& basis_t, int64_t n_fft, int64_t hop, int64_t win) {
+  dev(x, "x");
+  TORCH_CHECK_VALUE(x.dim() == 2 && x.size(0) > 0, "bigcodec::stft_frames: x must be (B, T)");
+  TORCH_CHECK_VALUE(n_fft >= 2 && n_fft % 2 == 0 && win == n_fft && hop >= 1 && hop <= win,
+                    "bigcodec::stft_frames: needs an even n_fft == win >= hop >= 1");
+  req(x, basis_t, "basis_t");
+  TORCH_CHECK_VALUE(basis_t.dim() == 2 && basis_t.size(0) == n_fft && basis_t.size(1) == n_fft + 2,
+                    "bigcodec::stft_frames: basis_t must be (n_fft, n_fft + 2)");
+  const int64_t pad = (win - hop) / 2, T = x.size(1);
+  TORCH_CHECK_VALUE(T + 2 * pad >= n_fft, "bigcodec::stft_frames: the clip is shorter than one frame");
+  const int64_t F = (T + 2 * pad - n_fft) / hop + 1;
+  auto y = at::empty({x.size(0), n_fft + 2, F}, x.options());
+  ok(bc_stft_frames(x.data_ptr<float>(), basis_t.data_ptr<float>(), y.data_ptr<float>(), i32(x.size(0), "B"), T,
+                    i32(n_fft, "n_fft"), i32(hop, "hop"), i32(win, "win"), stream_of(x)),
+     "bc_stft_frames");
+  return y;
+}
+
+Tensor rmsnorm(const Tensor& x, const optional<Tensor>& weight, double eps, bool silu) {
+  dev(x, "x");
+  TORCH_CHECK_VALUE(x.dim() == 3 && x.numel() > 0, "bigcodec::rmsnorm: x must be a non-empty (B, C, T)");
+  const float* w = optf(x, weight, "weight");
+  if (w) TORCH_CHECK_VALUE(weight->numel() == x.size(1), "bigcodec::rmsnorm: weight must have C entries");
+  auto y = at::empty_like(x);
+  ok(bc_rmsnorm_fwd(x.data_ptr<float>(), w, y.data_ptr<float>(), i32(x.size(0), "B"), i32(x.size(1), "C"),
+                    i32(x.size(2), "T"), static_cast<float>(eps), silu ? 1 : 0, stream_of(x)),
+     "bc_rmsnorm_fwd");
+  return y;
+}
+
+Tensor dwconv_glu(const Tensor& x, const Tensor& weight, const optional<Tensor>& bias, int64_t pad_left) {
+  dev(x, "x");
+  TORCH_CHECK_VALUE(x.dim() == 3 && x.numel() > 0 && x.size(1) % 2 == 0, "bigcodec::dwconv_glu: x must be (B, 2C, T)");
+  const int64_t C = x.size(1) / 2;
+  req(x, weight, "weight");
+  TORCH_CHECK_VALUE(weight.dim() == 3 && weight.size(0) == C && weight.size(1) == 1,
+                    "bigcodec::dwconv_glu: weight must be (C, 1, K)");
+  const int64_t K = weight.size(2);
+  TORCH_CHECK_VALUE(K >= 1 && K <= 63 && pad_left >= 0 && pad_left < K, "bigcodec::dwconv_glu: 1 <= K <= 63, 0 <= pad_left < K");
+  const float* b = optf(x, bias, "bias");
+  if (b) TORCH_CHECK_VALUE(bias->numel() == C, "bigcodec::dwconv_glu: bias must have C entries");
+  auto y = at::empty({x.size(0), C, x.size(2)}, x.options());
+  ok(bc_dwconv_glu_fwd(x.data_ptr<float>(), weight.data_ptr<float>(), b, y.data_ptr<float>(), i32(x.size(0), "B"),
+                       i32(C, "C"), i32(x.size(2), "T"), i32(K, "K"), i32(pad_left, "pad_left"), stream_of(x)),
+     "bc_dwconv_glu_fwd");
+  return y;
+}
+
+Tensor swiglu(const Tensor& h) {
+  dev(h, "h");
+  TORCH_CHECK_VALUE(h.dim() == 3 && h.numel() > 0 && h.size(1) % 2 == 0, "bigcodec::swiglu: h must be (B, 2H, T)");
+  auto y = at::empty({h.size(0), h.size(1) / 2, h.size(2)}, h.options());
+  ok(bc_swiglu_fwd(h.data_ptr<float>(), y.data_ptr<float>(), i32(h.size(0), "B"), i32(h.size(1) / 2, "H"), h.size(2),
+                   stream_of(h)),
+     "bc_swiglu_fwd");
+  return y;
+}
+
+Tensor attention(const Tensor& qkv, const Tensor& rope, int64_t n_head, bool causal) {
+  dev(qkv, "qkv");
+  TORCH_CHECK_VALUE(qkv.dim() == 3 && qkv.numel() > 0 && n_head >= 1 && qkv.size(1) % (3 * n_head) == 0,
+                    "bigcodec::attention: qkv must be (B, 3 * n_head * D, T)");
+  const int64_t dim = qkv.size(1) / 3, D = dim / n_head, T = qkv.size(2);
+  TORCH_CHECK_VALUE(D == 32 || D == 64, "bigcodec::attention: head_dim must be 32 or 64, got ", D);
+  req(qkv, rope, "rope");
+  TORCH_CHECK_VALUE(rope.dim() == 3 && rope.size(0) >= T && rope.size(1) == D / 2 && rope.size(2) == 2,
+                    "bigcodec::attention: rope must be (>= T, D / 2, 2)");
+  auto y = at::empty({qkv.size(0), dim, T}, qkv.options());
+  ok(bc_attention_fwd(qkv.data_ptr<float>(), rope.data_ptr<float>(), y.data_ptr<float>(), i32(qkv.size(0), "B"),
+                      i32(n_head, "n_head"), i32(D, "head_dim"), i32(T, "T"), causal ? 1 : 0, stream_of(qkv)),
+     "bc_attention_fwd");
+  return y;
+}
+
+Tensor istft_head(const Tensor& x_pred, const Tensor& basis, const Tensor& window, int64_t hop) {
+  dev(x_pred, "x_pred");
+  TORCH_CHECK_VALUE(x_pred.dim() == 3 && x_pred.numel() > 0 && x_pred.size(1) >= 4 && x_pred.size(1) % 2 == 0,
+                    "bigcodec::istft_head: x_pred must be (B, n_fft + 2, F)");
+  const int64_t n_fft = x_pred.size(1) - 2, F = x_pred.size(2);
+  TORCH_CHECK_VALUE(n_fft % 2 == 0 && hop >= 1 && hop <= n_fft, "bigcodec::istft_head: needs an even n_fft >= hop >= 1");
+  req(x_pred, basis, "basis");
+  req(x_pred, window, "window");
+  TORCH_CHECK_VALUE(basis.dim() == 2 && basis.size(0) == n_fft + 2 && basis.size(1) == n_fft && window.numel() == n_fft,
+                    "bigcodec::istft_head: basis must be (n_fft + 2, n_fft), window (n_fft,)");
+  const int64_t pad = (n_fft - hop) / 2;
+  auto y = at::empty({x_pred.size(0), 1, (F - 1) * hop + n_fft - 2 * pad}, x_pred.options());
+  ok(bc_istft_head(x_pred.data_ptr<float>(), basis.data_ptr<float>(), window.data_ptr<float>(), y.data_ptr<float>(),
+                   i32(x_pred.size(0), "B"), i32(F, "F"), i32(n_fft, "n_fft"), i32(hop, "hop"), stream_of(x_pred)),
+     "bc_istft_head");
+  return y;
+}
+
 // Every op runs under a device guard of its first tensor argument (the data tensor), so the C ABI's launches
 // and the op's allocations land on that tensor's device even when it is not the current one (the ABI launches
 // on the current HIP device; c10 reports these tensors as "cuda", hence the masquerading guard).
@@ -817,6 +910,12 @@ TORCH_LIBRARY(bigcodec, m) {
   m.def("logmel_l1(Tensor ref, Tensor rec, Tensor? lens, Tensor basis, Tensor mel, int n_fft, float clamp_eps) -> Tensor");
   m.def("code_hist_(Tensor(a!) counts, Tensor codes, Tensor? lens) -> ()");
   m.def("stoi(Tensor clean, Tensor proc, Tensor? lens, Tensor? filt, Tensor basis, int up, int down) -> (Tensor, Tensor)");
+  m.def("stft_frames(Tensor x, Tensor basis_t, int n_fft, int hop, int win) -> Tensor");
+  m.def("rmsnorm(Tensor x, Tensor? weight, float eps, bool silu) -> Tensor");
+  m.def("dwconv_glu(Tensor x, Tensor weight, Tensor? bias, int pad_left) -> Tensor");
+  m.def("swiglu(Tensor h) -> Tensor");
+  m.def("attention(Tensor qkv, Tensor rope, int n_head, bool causal) -> Tensor");
+  m.def("istft_head(Tensor x_pred, Tensor basis, Tensor window, int hop) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
@@ -853,4 +952,10 @@ TORCH_LIBRARY_IMPL(bigcodec, CUDA, m) {
   m.impl("logmel_l1", &Guarded<&logmel_l1>::call);
   m.impl("code_hist_", &Guarded<&code_hist_>::call);
   m.impl("stoi", &Guarded<&stoi>::call);
+  m.impl("stft_frames", &Guarded<&stft_frames>::call);
+  m.impl("rmsnorm", &Guarded<&rmsnorm>::call);
+  m.impl("dwconv_glu", &Guarded<&dwconv_glu>::call);
+  m.impl("swiglu", &Guarded<&swiglu>::call);
+  m.impl("attention", &Guarded<&attention>::call);
+  m.impl("istft_head", &Guarded<&istft_head>::call);
 }

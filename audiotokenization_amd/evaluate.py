@@ -13,7 +13,7 @@ from typing import List, Optional
 import torch
 
 from .codec import _refuse_ragged
-from .extract import READ_AHEAD, BigCodecModel, build_lm, find_items, item_path, plan_batches
+from .extract import READ_AHEAD, BigCodecModel, build_lm, find_items, item_path, plan_batches, whole_clips_only
 from .metrics import RoundTripMetrics
 
 
@@ -25,7 +25,10 @@ def _as_model(model) -> BigCodecModel:
 
 
 def _ragged_ok(lm) -> bool:
-    """Whether the model takes ragged batches (antialias / a bidirectional ResLSTM refuse them: file by file then)."""
+    """Whether the model takes ragged batches (antialias / a bidirectional ResLSTM / the Conformer-STFT family refuse
+    them: file by file then)."""
+    if whole_clips_only(lm):
+        return False
     try:
         _refuse_ragged(lm.model["CodecEnc"])
         _refuse_ragged(lm.model["generator"])

@@ -488,6 +488,14 @@ def build_lm(save_path: str, device):
     return CodecLightningModule.from_checkpoint(ckpt_path, load_config(config_path)).to(device).eval()
 
 
+def whole_clips_only(lm) -> bool:
+    """Whether either side of the model is of the Conformer-STFT family, which takes no ragged batch."""
+    from .conformer import ConformerDecoderISTFT, ConformerEncoderSTFT
+
+    return (isinstance(lm.model["CodecEnc"], ConformerEncoderSTFT) or
+            isinstance(lm.model["generator"], ConformerDecoderISTFT))
+
+
 READ_AHEAD = 8  # run_extraction(batch > 1): the window of decoded files that is sorted by length, in batches
 
 
@@ -603,6 +611,8 @@ def run_extraction(lm, items, output_dir: str, sample_rate: Optional[int], durat
 
     if batch < 1:
         raise ValueError("batch must be >= 1")
+    if whole_clips_only(lm):
+        batch = 1  # the Conformer-STFT family refuses lengths= (global attention): file by file
     model = BigCodecModel(lm)
     lo, hi = shard_range(len(items), rank, world)
     mine = items[lo:hi]

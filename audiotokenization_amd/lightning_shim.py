@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from .codec import BigCodecDecoder, BigCodecEncoder
-from .config import AttrDict, decoder_kwargs, encoder_kwargs
+from .config import AttrDict, decoder_kwargs, decoder_type, encoder_kwargs, encoder_type
+from .conformer import ConformerDecoderISTFT, ConformerEncoderSTFT
 
 _KEEP = ("encoder.", "decoder.")
 
@@ -28,8 +29,12 @@ class CodecLightningModule(nn.Module):
         self.construct_model()
 
     def construct_model(self):
-        self.encoder = BigCodecEncoder(**encoder_kwargs(self.cfg.model.codec_encoder))
-        self.decoder = BigCodecDecoder(**decoder_kwargs(self.cfg.model.codec_decoder))
+        """lightning_module.py:87-165: either side is a BigCodec or a Conformer-STFT model, by its `type`."""
+        enccfg, deccfg = self.cfg.model.codec_encoder, self.cfg.model.codec_decoder
+        enc_cls = ConformerEncoderSTFT if encoder_type(enccfg) == "conformer_stft" else BigCodecEncoder
+        dec_cls = ConformerDecoderISTFT if decoder_type(deccfg) == "conformer_istft" else BigCodecDecoder
+        self.encoder = enc_cls(**encoder_kwargs(enccfg))
+        self.decoder = dec_cls(**decoder_kwargs(deccfg))
 
     @property
     def model(self):

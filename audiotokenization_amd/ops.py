@@ -27,7 +27,8 @@ _ns = None
 OPS = ("conv1d", "conv_transpose1d", "resunit", "snake", "aa_snake", "aa_snake_ex", "tanh", "reslstm", "reslstm_bidir", "vq_prepare_codebook", "vq",
        "vq_argmin", "vq2emb", "vq2emb_add_", "rvq_update_", "vq2emb_ct", "fsq", "fsq_codes", "stream_window", "resample_sinc", "synth_clips_",
        "zero_tail_", "si_snr", "logmel_l1", "code_hist_", "stream_window_slots_", "lstm_state_gather", "lstm_state_scatter_",
-       "stream_window_slots_lens_", "reslstm_lens", "stoi", "stream_window_la", "stream_window_slots_la_")
+       "stream_window_slots_lens_", "reslstm_lens", "stoi", "stream_window_la", "stream_window_slots_la_",
+       "stft_frames", "rmsnorm", "dwconv_glu", "swiglu", "attention", "istft_head")
 
 
 def load():
@@ -208,6 +209,32 @@ def _register_fakes():
     @reg("bigcodec::code_hist_")
     def _code_hist(counts, codes, lens):
         return None
+
+    @reg("bigcodec::stft_frames")
+    def _stft_frames(x, basis_t, n_fft, hop, win):
+        pad = (win - hop) // 2
+        return _new(x, (x.shape[0], n_fft + 2, (x.shape[1] + 2 * pad - n_fft) // hop + 1))
+
+    @reg("bigcodec::rmsnorm")
+    def _rmsnorm(x, weight, eps, silu):
+        return _new(x, x.shape)
+
+    @reg("bigcodec::dwconv_glu")
+    def _dwconv_glu(x, weight, bias, pad_left):
+        return _new(x, (x.shape[0], x.shape[1] // 2, x.shape[2]))
+
+    @reg("bigcodec::swiglu")
+    def _swiglu(h):
+        return _new(h, (h.shape[0], h.shape[1] // 2, h.shape[2]))
+
+    @reg("bigcodec::attention")
+    def _attention(qkv, rope, n_head, causal):
+        return _new(qkv, (qkv.shape[0], qkv.shape[1] // 3, qkv.shape[2]))
+
+    @reg("bigcodec::istft_head")
+    def _istft_head(x_pred, basis, window, hop):
+        n_fft = x_pred.shape[1] - 2
+        return _new(x_pred, (x_pred.shape[0], 1, (x_pred.shape[2] - 1) * hop + n_fft - 2 * ((n_fft - hop) // 2)))
 
     @reg("bigcodec::stoi")
     def _stoi(clean, proc, lens, filt, basis, up, down):

@@ -57,11 +57,21 @@ from .conv import CausalConvTranspose1d, ConvTranspose1dWN
 from .modules import _as_input
 
 
+def _refuse_global_attention(model) -> None:
+    """The Conformer-STFT family attends over the whole clip (and its causal variant over the whole past): no bounded
+    state to carry, so no streaming class takes it."""
+    from .conformer import SelfAttention
+
+    if any(isinstance(m, SelfAttention) for m in model.modules()):
+        raise NotImplementedError("the Conformer-STFT family attends over the whole clip: streaming is not built for it")
+
+
 class StreamingEncoder:
     """Wraps a causal BigCodecEncoder; `push(x (B, 1, n))` returns the latents (B, D, n / hop) of the
     chunk.  `reset()` starts a new stream.  The batch size is fixed per stream."""
 
     def __init__(self, encoder):
+        _refuse_global_attention(encoder)
         convs = [m for m in encoder.modules() if hasattr(m, "causal_pad")]
         # every conv that looks at more than one input sample must be causal (the ResidualUnits' k=1
         # convs are plain, padding 0, in the reference too)
@@ -170,6 +180,7 @@ class StreamingDecoder(StreamingEncoder):
     (h, c)."""
 
     def __init__(self, decoder):
+        _refuse_global_attention(decoder)
         convs = [m for m in decoder.modules() if hasattr(m, "causal_pad")]
         if not convs or any(m.causal_pad is None and (m.kernel_size > 1 or m.padding) for m in convs):
             raise ValueError("streaming needs a causal decoder (causal=True)")
@@ -278,7 +289,8 @@ def _unit_stage(ru):
 def lookahead_stages(model):
     """The lazy stages of a BigCodecEncoder / BigCodecDecoder in flow order: one per producer of the model's own
     per-layer length table (frame_lengths / sample_lengths with per_layer=True, rows 1 on).  Refuses what looks ahead
-    without bound: anti-aliased activations and a bidirectional ResLSTM."""
+    without bound: anti-aliased activations, a bidirectional ResLSTM and the Conformer-STFT family."""
+    _refuse_global_attention(model)
     if any(getattr(m, "antialias", False) for m in model.modules()):
         raise NotImplementedError("anti-aliased activations replicate-pad at the clip's end: not streamable")
     if any(isinstance(m, ResLSTM) and m.lstm.bidirectional for m in model.modules()):

@@ -13,6 +13,8 @@ Weight spec (per state_dict entry, keyed by its name):
   *.alpha / *.beta (Snake, log scale)    uniform(-0.5, 0.5)
   *._codebook.weight                     uniform(-1, 1)
   *.filter (anti-alias buffers)          left as constructed (deterministic Kaiser-sinc)
+  *.window (STFT / ISTFT buffers)        left as constructed (Hann)
+  *.weight, 1-D (RMSNorm gain)           uniform(0.75, 1.25)
 Clip spec: x[i, n] = (splitmix64(0xB16C0DEC ^ (i << 32) ^ n) >> 40) * 2^-24 - 0.5   (exact fp32)
 """
 from __future__ import annotations
@@ -70,7 +72,7 @@ def synth_state_dict(template: Mapping[str, "np.ndarray | object"], seed: int = 
     out: Dict[str, np.ndarray] = {}
     # pass 1: weights (v first so g can use ||v||)
     for k, shp in shapes.items():
-        if k.endswith(".filter"):
+        if k.endswith(".filter") or k.endswith(".window"):
             v = template[k]
             arr = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
             out[k] = arr.astype(np.float32).copy()
@@ -87,6 +89,8 @@ def synth_state_dict(template: Mapping[str, "np.ndarray | object"], seed: int = 
             fan_in = int(np.prod(shp[1:]))
             b = 1.0 / np.sqrt(fan_in)
             out[k] = _uniform(k, shp, -b, b, seed)
+        elif k.endswith(".weight") and len(shp) == 1:
+            out[k] = _uniform(k, shp, 0.75, 1.25, seed)
     for k, shp in shapes.items():
         if k in out:
             continue

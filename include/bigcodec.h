@@ -460,6 +460,48 @@ long long bc_stoi_workspace_bytes(int B, long long T, int up, int down);
 int bc_stoi(const float* clean, const float* proc, const int* lens, const float* filt, int up, int down, int half_len,
             const float* basis, float* out, int* kept, void* workspace, int B, long long T, void* stream);
 
+/* ---- Conformer-STFT codec family (additive under ABI 18) -----------------------------------
+ * Everything of ConformerEncoderSTFT / ConformerDecoderISTFT that is not a Linear or a 1x1 conv (those run on
+ * bc_conv1d_fwd).  Activations are [B][C][T] fp32; the arithmetic is fp32 VALU in every precision mode, the long sums
+ * fold 16-term fp32 partial sums into an fp64 total.  Each call checks its arguments on the host (1 / 3) before it
+ * launches.
+ * bc_stft_frames: vq/codec_encoder.py:108-122 (F.pad by (win - hop) / 2 per side, torch.stft center=False) and the
+ *   real / imaginary concatenation of :188-192.  x[B][T]; basis_t[n_fft][n_fft + 2], column c < bins = n_fft / 2 + 1:
+ *   w[n] cos(2 pi c n / n_fft), column bins + c: -w[n] sin(...), w the periodic Hann window (built in float64 on the
+ *   host: audiotokenization_amd/conformer.py); y[B][n_fft + 2][F], F = (T + 2 ((win - hop) / 2) - n_fft) / hop + 1.
+ *   3 for win != n_fft or an odd n_fft.
+ * bc_rmsnorm_fwd: vq/module.py:357-370 over the channels of every (b, t): (x * rsqrt(mean_c x^2 + eps)) * w[c], in that
+ *   order; w may be NULL (no gain); silu != 0 applies x * sigmoid(x) to the result (module.py:490-491).
+ * bc_dwconv_glu_fwd: nn.GLU(dim=1) and the depthwise conv of ConformerConvModule (vq/module.py:476-480, 488-489).
+ *   x[B][2 C][T] (pointwise_conv1's output), w[C][K], bias[C] or NULL, y[B][C][T]:
+ *   y[c][t] = bias[c] + sum_k w[c][k] g[c][t + k - pad_left], g = x[c] * sigmoid(x[C + c]), zero outside [0, T).
+ *   pad_left = (K - 1) / 2 is padding='same' (the right pad is K - 1 - pad_left), K - 1 the CausalConv1d.  K <= 63.
+ * bc_swiglu_fwd: F.silu(w1 x) * (w3 x) of FeedForward (vq/module.py:468) over h[B][2 H][T], the output of w1 and w3
+ *   stacked into one conv; y[B][H][T].
+ * bc_attention_fwd: SelfAttention.forward's manual branch between qkv_proj and out_proj (vq/module.py:421-449).
+ *   qkv[B][3 n_head D][T], channel s n_head D + h D + d (s: q, k, v); rope[>= T][D / 2][2]: torch.view_as_real of
+ *   precompute_freqs_cis (module.py:372-377); y[B][n_head D][T].  q and k are RMS-normalised over D (eps 1e-6) and
+ *   rotated, then softmax(q k^T / sqrt(D)) v with the keys <= the query when causal.  Keys and values pass through LDS
+ *   in tiles and the softmax is online: no T x T array exists.  head_dim 32 or 64 (3 otherwise).
+ *   bc_attention_tiles: the queries per workgroup and the keys per LDS tile (the tests' edge lengths).
+ * bc_istft_head: ISTFTHead.forward after self.out and ISTFT.forward with padding="same" (vq/codec_decoder.py:171-213,
+ *   261-274).  x_pred[B][n_fft + 2][F]: rows [0, bins) log-magnitudes, rows [bins, 2 bins) phases;
+ *   S = min(exp(.), 100) (cos p + i sin p) (own range reduction up to |p| < 39000, libm beyond); basis[n_fft + 2][n_fft]:
+ *   the inverse real DFT (backward norm, DC and Nyquist imaginary rows zero) times the window, built in float64 on
+ *   the host; window[n_fft].  y[B][(F - 1) hop + n_fft - 2 ((n_fft - hop) / 2)]: the overlap-add cropped by
+ *   (n_fft - hop) / 2 per side and divided by the sum of window^2 over the frames that overlap each sample. */
+int bc_stft_frames(const float* x, const float* basis_t, float* y, int B, long long T, int n_fft, int hop, int win,
+                   void* stream);
+int bc_rmsnorm_fwd(const float* x, const float* w, float* y, int B, int C, int T, float eps, int silu, void* stream);
+int bc_dwconv_glu_fwd(const float* x, const float* w, const float* bias, float* y, int B, int C, int T, int K,
+                      int pad_left, void* stream);
+int bc_swiglu_fwd(const float* h, float* y, int B, int H, long long T, void* stream);
+int bc_attention_tiles(int* q_tile, int* kv_tile);
+int bc_attention_fwd(const float* qkv, const float* rope, float* y, int B, int n_head, int head_dim, int T, int causal,
+                     void* stream);
+int bc_istft_head(const float* x_pred, const float* basis, const float* window, float* y, int B, int F, int n_fft,
+                  int hop, void* stream);
+
 /* ---- Bounds-checked debug build (no reference counterpart: SURVEY.md §5 row 2) ------------------------------
  * libbigcodec_hip.so built with -DBC_DEBUG (build_lib.build(debug=True) -> audiotokenization_amd/_debug/, loaded by
  * the Python package when BIGCODEC_DEBUG=1) checks the indices of the kernels' computed global accesses (conv /
