@@ -633,7 +633,7 @@ int bc_vq2emb(const long long* idx, long long idx_stride, const float* codebook,
   if ((w_out == nullptr) != (b_out == nullptr)) return BC_ERR_ARG;
   if (!w_out && D != dim) return BC_ERR_ARG;
   if (dim != 8) return BC_ERR_UNSUPPORTED;
-  return vq2emb_launch(idx, idx_stride, codebook, w_out, b_out, emb, N, D, accumulate, S(stream));
+  return vq2emb_launch(idx, idx_stride, codebook, w_out, b_out, emb, N, D, n_codes, accumulate, S(stream));
 }
 
 int bc_fsq_fwd(const float* z, const float* w_in, const float* b_in, const float* w_out, const float* b_out,

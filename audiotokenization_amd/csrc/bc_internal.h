@@ -167,7 +167,7 @@ int fsq_codes_launch(const void* idx, int idx_bits, const int* levels, const flo
 int vq2emb_ct_launch(const long long* idx, int nq, const float* cb, const float* w_out, const float* b_out,
                      float* emb, int B, int T, int D, int n_codes, hipStream_t st);
 int vq2emb_launch(const long long* idx, long long idx_stride, const float* cb, const float* w_out,
-                  const float* b_out, float* emb, long long N, int D, int accumulate,
+                  const float* b_out, float* emb, long long N, int D, int n_codes, int accumulate,
                   hipStream_t st);
 int rvq_update_launch(float* residual, float* out, const float* q, long long n, int first,
                       hipStream_t st);

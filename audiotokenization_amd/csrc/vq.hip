@@ -183,25 +183,30 @@ __global__ void __launch_bounds__(256) vq_argmin_kernel(const float* __restrict_
 }
 
 // emb[n][d] = b_out[d] + sum_q W_out[d][q] * cb[idx[n]][q]     (output (N, D), as vq2emb returns)
+// An index outside [0, n_codes) yields NaN for its row, also when accumulating (a bad token never passes
+// silently), and reads row 0 instead: no out-of-range read (as vq2emb_ct_kernel below).
 __global__ void vq2emb_kernel(const long long* __restrict__ idx, long long idx_stride,
                               const float* __restrict__ cb, const float* __restrict__ w_out,
                               const float* __restrict__ b_out, float* __restrict__ emb, long long N,
-                              int D, int accumulate) {
+                              int D, int n_codes, int accumulate) {
   const long long total = N * D;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
     const long long n = e / D;
     const int d = (int)(e % D);
     const long long k = idx[n * idx_stride];
+    const bool ok = k >= 0 && k < n_codes;
+    const float* row = cb + (ok ? k : 0) * VQ_DIM;
     float v;
     if (w_out) {
       float acc = 0.f;
 #pragma unroll
-      for (int q = 0; q < VQ_DIM; ++q) acc = fmaf(w_out[d * VQ_DIM + q], cb[k * VQ_DIM + q], acc);
+      for (int q = 0; q < VQ_DIM; ++q) acc = fmaf(w_out[d * VQ_DIM + q], row[q], acc);
       v = acc + b_out[d];
     } else {
-      v = cb[k * VQ_DIM + d];  // proj=False: embed_code only
+      v = row[d];  // proj=False: embed_code only
     }
+    v = ok ? v : __builtin_nanf("");
     emb[e] = accumulate ? emb[e] + v : v;
   }
 }
@@ -460,12 +465,12 @@ int vq_argmin_launch(const float* ze, const float* cbn, const float* csq, long l
 }
 
 int vq2emb_launch(const long long* idx, long long idx_stride, const float* cb, const float* w_out,
-                  const float* b_out, float* emb, long long N, int D, int accumulate,
+                  const float* b_out, float* emb, long long N, int D, int n_codes, int accumulate,
                   hipStream_t st) {
   const long long total = N * D;
   if (total == 0) return BC_OK;
   hipLaunchKernelGGL(vq2emb_kernel, dim3(grid_for(total, 256)), dim3(256), 0, st, idx, idx_stride, cb,
-                     w_out, b_out, emb, N, D, accumulate);
+                     w_out, b_out, emb, N, D, n_codes, accumulate);
   BC_CHECK_LAUNCH();
   return BC_OK;
 }

@@ -240,7 +240,8 @@ int bc_reslstm_bidir_fwd(const float* x, float* out, int B, int D, int T, int nu
  *   z_e the indices equal the reference's ("VQ exactness").
  * bc_vq2emb: FactorizedVectorQuantize.vq2emb (:78-81): idx[n*idx_stride] -> emb [N][D] (= (B,T,D)
  *   as the reference returns); w_out == NULL means proj=False (emb = codebook rows, D == dim);
- *   accumulate != 0 adds into emb (ResidualVQ.vq2emb sum, residual_vq.py:42-48).
+ *   accumulate != 0 adds into emb (ResidualVQ.vq2emb sum, residual_vq.py:42-48); an index outside
+ *   [0, n_codes) gives NaN, never an out-of-range read.
  * bc_rvq_update: ResidualVQ bookkeeping (residual_vq.py:31-33): residual -= q; out (+)= q. */
 int bc_vq_prepare_codebook(const float* codebook, float* codebook_norm, float* codebook_sq,
                            int n_codes, int dim, void* stream);
