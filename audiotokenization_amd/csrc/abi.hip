@@ -273,7 +273,7 @@ int bc_convT1d_fwd_ws(const float* x, const float* const* w_phases, const float*
     a.Cin = Cin; a.Tin = Tin; a.Cout = Cout; a.Nout = nout;
     a.K = Kp; a.s = 1; a.d = 1; a.pl = Kp - 1 - q_lo;  // as bc_convT1d_fwd
     a.yT = Q4; a.ostride = 1; a.ooff = 0; a.epi = 0;
-    if (a.pl < 0) return BC_ERR_UNSUPPORTED;
+    if (a.pl < 0) return BC_ERR_UNSUPPORTED;  // padding > s * (Kp - 1), as bc_convT1d_fwd (at r = 0: nothing written)
     const int rc = conv_launch(a, B, cfg, S(stream));
     if (rc != BC_OK) return rc;
   }
@@ -310,7 +310,10 @@ int bc_convT1d_fwd(const float* x, const float* const* w_phases, const float* bi
     // q = n + q_lo
     a.K = Kp; a.s = 1; a.d = 1; a.pl = Kp - 1 - q_lo;
     a.yT = Tout; a.ostride = s; a.ooff = s * q_lo - p + r; a.epi = 0;
-    if (a.pl < 0) return BC_ERR_UNSUPPORTED;  // padding >= K: not a DecoderBlock shape
+    // padding > s * (Kp - 1): phase 0 would start at q_lo = ceil(p / s) > Kp - 1, a negative left pad of its
+    // stride-1 conv (e.g. K = s = 4, p = 1; not "padding >= K").  Phase 0 has the largest q_lo, so nothing has
+    // been launched yet.  Not a DecoderBlock shape.
+    if (a.pl < 0) return BC_ERR_UNSUPPORTED;
     const int rc = conv_launch(a, B, cfg, S(stream));
     if (rc != BC_OK) return rc;
   }

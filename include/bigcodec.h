@@ -108,7 +108,9 @@ int bc_resunit_fwd_snake_in(const float* x_raw, const float* in_snake_alpha_exp,
  * a HOST array of `stride` device pointers.  Output length Tout = (Tin-1)*stride - 2*padding + K +
  * output_padding (the caller passes Tout, which carries output_padding); DecoderBlock non-causal:
  * padding = stride/2 + stride%2, output_padding = stride%2.  Causal (crop of the last `stride`
- * samples): padding = 0, Tout = (Tin-1)*stride + K - stride.  Epilogue as bc_conv1d_fwd. */
+ * samples): padding = 0, Tout = (Tin-1)*stride + K - stride.  Epilogue as bc_conv1d_fwd.
+ * padding > stride * (Kp - 1) (e.g. K = stride = 4, padding = 1) returns BC_ERR_UNSUPPORTED from both
+ * entry points, with nothing written. */
 int bc_convT1d_phase_taps(int K, int stride);
 int bc_convT1d_fwd(const float* x, const float* const* w_phases, const float* bias,
                    const float* out_snake_alpha_exp, const float* out_snake_inv_beta, float* y,
