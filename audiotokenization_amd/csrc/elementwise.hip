@@ -10,13 +10,10 @@
 //                     the 2T intermediate never leaves LDS.
 //  transpose kernels: [B][C][T] <-> [C][T][B] layouts around the ResLSTM (vq/module.py:160-166).
 //  synth_clips      : counter-hash white noise generated in HBM.
-//  stream_window    : a causal stream's [carried context | chunk] window (+ Snake) and its next context.
-//  stream_window_la : the window of a look-ahead stream's lazy stage: carry in and carry out of different lengths, the
-//                     layer's right zero padding at the flush (streaming.py LookaheadEncoder / LookaheadDecoder).
-//  stream_window_slots / lstm_state_gather / lstm_state_scatter : the same step for a pool of independent sessions,
-//                     the carried state indexed by per-entry pool rows (streaming.py StreamPool).
-//  stream_window_slots_lens : stream_window_slots with a chunk length per entry (zeros past it, the context that ends
-//                     there), for a pool push whose sessions deliver different numbers of hops.
+//  window_kernel    : a stream's [carried columns | new columns (+ Snake) | zeros] window and its next carry, for the
+//                     five bc_stream_window* entry points: dense carries (a causal or a look-ahead stream), or pool
+//                     rows per entry (streaming.py StreamPool / LookaheadPool), chosen at compile time.
+//  lstm_state_gather / lstm_state_scatter : a pool's carried ResLSTM state, indexed by per-entry pool rows.
 //  zero_tail        : zeros from each clip's own length to the padded end of a ragged batch's rows.
 #include <algorithm>
 #include "bc_common.h"
@@ -194,38 +191,145 @@ int snake_launch(const float* x, const float* sa, const float* sb, float* y, int
   return BC_OK;
 }
 
-// Streaming context window (streaming.py, causal streaming encode / decode): for each (b, c) row
-//   win[j]     = j < P ? ctx[j] : act(x[j - P])   (j < P + n: the [carried context | chunk] input of a causal conv,
-//                                                  or of a whole one-launch ResidualUnit)
-//   ctx_out[i] = win[n + i]                        (i < P: the context the next chunk carries)
-// in one pass.  act = SnakeBeta through snake() (bit-identical to snake_kernel's pairs and to the convs' Snake
-// epilogue) or the identity; a missing ctx reads zeros (a stream's first chunk: the causal conv's zero padding,
-// and snake(0) = 0, so zeros are the same before and after the activation).  x may be a strided view (row pitch
-// xT, batch pitch xbs): a ResidualUnit run over its own window hands its last n columns on without a copy.
+// The streaming window (streaming.py): one kernel behind the five bc_stream_window*
+// entry points.  A stage of a stream is a lazy valid conv (or a whole one-launch ResidualUnit) over
+// [the columns it carried | the new columns | zeros], and it hands on the columns it has not finished with.  For each
+// (b, c) row, with W window columns:
+//   win[j] = j < ci ? (cr ? cr[j] : 0) : j < ci + n ? act(x[xo + j - ci]) : 0      (j < W)
+//   nr[i]  = win[keep + i]   for i < co                                            (co == 0: nothing stored)
+// act = SnakeBeta through snake() (bit-identical to snake_kernel's pairs and to the convs' Snake epilogue) or the
+// identity.  A missing carry reads zeros (a stream's first chunk: the conv's left zero padding; snake(0) = 0, so
+// zeros are the same before and after the activation).  x may be a strided view (row pitch xT, batch pitch xbs: a
+// ResidualUnit run over its own window hands its last columns on without a copy); it is never dereferenced with
+// n == 0 and never at or past an entry's own n (it may hold NaN there).  The zeros behind ci + n are a layer's right
+// zero padding at a flush and the tail behind a short entry alike.  A carry never holds one of them: keep + co <=
+// ci + n, which with keep < ci reaches back into the old carry.
+// Who sets what (a Rows descriptor, passed by value, turns a row into a WinRow):
+//   WinDense<true>   bc_stream_window          ci = co = P, n, xo = 0, keep = n, W = P + n   kernel arguments only:
+//   WinDense<false>  bc_stream_window_la       ci = Pin, co = Pout, keep = Pin + n - Pout,   cr = ctx + row * Pin,
+//                                              W = Pin + n + R                               nr = ctx_out + row * Pout
+//   WinSlots<false>  bc_stream_window_slots    ci = co = P, n = keep = the chunk, W = P + n  pool rows src[b] / dst[b]
+//   WinSlots<true>   bc_stream_window_slots_lens  n = keep = clamp(lens[b] * unit, 0, chunk) and lens[b]
+//   WinSlotsLa       bc_stream_window_slots_la cin, n, xoff, keep, cout [b], any W           pool rows src[b] / dst[b]
+// The dense rows read no per-entry array: a dependent src[b] / dst[b] load in front of this little work costs a
+// quarter of the kernel, hence a template and not a run-time switch.  Pool rows: pool is
+// [pool_rows][C][pitch], src[b] < 0 reads the carry as zeros (a fresh session), dst[b] < 0 stores nothing (co = 0:
+// the padding entries of a graph replay); the values come from device memory, so the debug build checks them against
+// the pool and a bad one is skipped.  WinSlotsLa clamps cin and cout to [0, Pmax], xoff to [0, xn] and n to [0, min(W - cin,
+// xn - xoff)], so no index array can take an access out of x, win or a pool row.
+// IN-PLACE HAZARD: with keep < ci, carry element i of a row is read by the thread that writes window column i and
+// overwritten by the thread at column keep + i, which may sit in another workgroup, so a pool row must never be read
+// and written in one launch.  The HOST guarantees it: the src and dst row sets of a launch are disjoint and dst holds
+// no row twice (the pools' ping-pong rows 2s / 2s + 1 per session); the kernel cannot check it.
 // 2-D grid (three 64-bit divisions per element): y walks the (b, c) rows (one 32-bit division per row),
-// x the W = P + n window columns of a row
-__global__ void __launch_bounds__(256) stream_window_kernel(const float* __restrict__ x, long long xbs, long long xT,
-                                                            const float* __restrict__ ctx, const float* __restrict__ sa,
-                                                            const float* __restrict__ sb, float* __restrict__ win,
-                                                            float* __restrict__ ctx_out, int C, int n, int P, int rows) {
-  const int W = P + n;
+// x the W columns of a row.  One float per lane, coalesced along the row: the three streams of a row start at
+// row * W, row * pitch and a strided view's column offset (3d behind a one-launch ResidualUnit), with carries of
+// 6d = 6, 18, 54 columns in steady state, so they are never 16-byte aligned together and no stage would take a vector
+// path.
+struct WinRow {
+  const float* cr;  // the carried columns (null: zeros)
+  float* nr;        // where the next carry goes (not dereferenced with co == 0)
+  int ci, n, xo, keep, co;
+};
+
+// (pin / pout: the pitch of a carry row read / written; xn: the columns of x an entry may touch; tail: zeros may
+// follow the new columns, W > ci + n.)  What a launcher knows is a template argument, because these kernels are bound
+// by the instructions of a wave, not by bytes: Plain is bc_stream_window's pout == pin, W == pin + xn; Lens is
+// bc_stream_window_slots_lens' length per entry.
+template <bool Plain>
+struct WinDense {
+  static constexpr bool tail = !Plain;
+  const float* ctx;
+  float* ctx_out;
+  int pin, xn, pout;
+  __device__ WinRow row(int row, int, int, int) const {
+    // (a null ctx_out comes with a carry out of no columns, so it is never dereferenced)
+    if (Plain) {
+      const long long at = (long long)row * pin;
+      return {ctx ? ctx + at : nullptr, ctx_out + at, pin, xn, 0, xn, pin};
+    }
+    return {ctx ? ctx + (long long)row * pin : nullptr, ctx_out + (long long)row * pout, pin, xn, 0, pin + xn - pout,
+            pout};
+  }
+};
+
+template <bool Lens>
+struct WinSlots {
+  static constexpr bool tail = Lens;
+  float* pool;
+  const int *src, *dst, *lens;  // (lens is read with Lens only)
+  int unit, pin, pout, xn, pool_rows;
+  __device__ WinRow row(int, int b, int c, int C) const {
+    const int s = src[b], d = dst[b];
+    int L = xn;
+    if (Lens) {
+      const long long want = (long long)lens[b] * unit;
+      L = want < 0 ? 0 : want > xn ? xn : (int)want;
+    }
+    return {(s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * pin : nullptr,
+            pool + ((long long)max(d, 0) * C + c) * pin, pin, L, 0, L, (d >= 0 && BC_DOK(d < pool_rows)) ? pin : 0};
+  }
+};
+
+struct WinSlotsLa {
+  static constexpr bool tail = true;
+  float* pool;
+  const int *src, *dst, *cin, *nnew, *xoff, *keep, *cout;
+  int W, pin, pout, xn, pool_rows;
+  __device__ WinRow row(int, int b, int c, int C) const {
+    const int s = src[b], d = dst[b];
+    const int ci = min(max(cin[b], 0), pin), co = min(max(cout[b], 0), pin);
+    const int xo = min(max(xoff[b], 0), xn);
+    const int n = min(max(nnew[b], 0), min(W - ci, xn - xo));  // (W - ci < 0: no new column, the carry fills the row)
+    return {(s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * pin : nullptr,
+            pool + ((long long)max(d, 0) * C + c) * pin, ci, n, xo, keep[b],
+            (d >= 0 && BC_DOK(d < pool_rows)) ? co : 0};
+  }
+};
+
+template <class Rows>
+__global__ void __launch_bounds__(256) window_kernel(const Rows rows_of, const float* __restrict__ x, long long xbs,
+                                                     long long xT, const float* __restrict__ sa,
+                                                     const float* __restrict__ sb, float* __restrict__ win, int C,
+                                                     int W, int rows) {
   for (int row = blockIdx.y; row < rows; row += gridDim.y) {
     const int b = row / C, c = row - b * C;
-    const float* xr = x + (long long)b * xbs + (long long)c * xT;
+    const WinRow r = rows_of.row(row, b, c, C);
+    const float* __restrict__ cr = r.cr;
+    float* __restrict__ nr = r.nr;
+    const int S = r.ci + r.n;
+    const float* xr = x + (long long)b * xbs + (long long)c * xT + r.xo;
     float* wr = win + (long long)row * W;
     const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
     for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
-      float v;
-      if (j < P) {
-        v = ctx ? ctx[(long long)row * P + j] : 0.f;
-      } else {
-        v = xr[j - P];
-        if (sa) v = snake(v, a_, b_);
+      float v = 0.f;
+      if (j < r.ci) {
+        if (cr && BC_DOK(j >= 0 && j < rows_of.pin && row < rows)) v = cr[j];
+      } else if (!Rows::tail || j < S) {
+        if (BC_DOK(j - r.ci >= 0 && r.xo + (j - r.ci) < rows_of.xn && r.xo + (j - r.ci) < xT)) {
+          v = xr[(unsigned)(j - r.ci)];
+          if (sa) v = snake(v, a_, b_);
+        }
       }
-      wr[j] = v;
-      if (j >= n) ctx_out[(long long)row * P + (j - n)] = v;
+      if (BC_DOK(j >= 0 && j < W && row < rows)) wr[j] = v;
+      // keep <= j < keep + co in one compare (j < S: a carry that reaches into the zeros is a host bug the debug
+      // build reports)
+      if ((unsigned)j - (unsigned)r.keep < (unsigned)r.co &&
+          BC_DOK(j - r.keep >= 0 && j - r.keep < rows_of.pout && j < S))
+        nr[(unsigned)j - (unsigned)r.keep] = v;
     }
   }
+}
+
+// (the launchers have checked that rows and W fit an int, and W >= 1)
+template <class Rows>
+static int launch_window(const Rows& rows_of, const float* x, long long xbs, long long xT, const float* sa,
+                         const float* sb, float* win, int C, long long W, long long rows, hipStream_t st) {
+  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
+  hipLaunchKernelGGL(window_kernel<Rows>, dim3(gx, gy), dim3(256), 0, st, rows_of, x, xbs, xT, sa, sb, win, C, (int)W,
+                     (int)rows);
+  BC_CHECK_LAUNCH();
+  return BC_OK;
 }
 
 int stream_window_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa, const float* sb,
@@ -235,50 +339,7 @@ int stream_window_launch(const float* x, long long xbs, long long xT, const floa
   const long long rows = (long long)B * C, W = (long long)P + n;
   if (rows == 0) return BC_OK;
   if (rows > 0x7fffffffLL || W > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
-  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
-  hipLaunchKernelGGL(stream_window_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, ctx, sa, sb, win, ctx_out, C, n,
-                     P, (int)rows);
-  BC_CHECK_LAUNCH();
-  return BC_OK;
-}
-
-// Look-ahead streaming (streaming.py LookaheadEncoder / LookaheadDecoder): a stage of a non-causal
-// model is a lazy valid conv that carries the input columns it has not finished with, so its carry grows during the
-// first pushes (Pout > Pin), may reach back into the old carry when a chunk is short (Pout > n), and at the flush the
-// layer's own right zero padding follows the last sample.  For each (b, c) row, with S = Pin + n:
-//   win[j]     = j < Pin ? ctx[j] : j < S ? act(x[j - Pin]) : 0.0f      (j < S + R)
-//   ctx_out[i] = win[S - Pout + i]                                       (i < Pout <= S: never a right zero)
-// Same snake(), same missing-ctx zeros, same strided x and same 2-D grid as stream_window_kernel, whose values it
-// reproduces bit for bit with Pin == Pout, R == 0.  n == 0 (a flush without new input) never dereferences x.
-// Accesses are one float per lane, coalesced along the row: the three streams of a row start at row * (S + R),
-// row * Pin and a strided view's column offset (3d behind a one-launch ResidualUnit), with Pin = 6d = 6, 18, 54 in
-// steady state, so they are never 16-byte aligned together and a vector path would not be taken by any stage.
-__global__ void __launch_bounds__(256) stream_window_la_kernel(const float* __restrict__ x, long long xbs, long long xT,
-                                                               const float* __restrict__ ctx, const float* __restrict__ sa,
-                                                               const float* __restrict__ sb, float* __restrict__ win,
-                                                               float* __restrict__ ctx_out, int C, int n, int Pin, int R,
-                                                               int Pout, int rows) {
-  const int S = Pin + n, W = S + R, keep = S - Pout;
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int b = row / C, c = row - b * C;
-    const float* xr = x + (long long)b * xbs + (long long)c * xT;
-    float* wr = win + (long long)row * W;
-    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
-      float v = 0.f;
-      if (j < Pin) {
-        if (ctx && BC_DOK(j >= 0 && row < rows)) v = ctx[(long long)row * Pin + j];
-      } else if (j < S) {
-        if (BC_DOK(j - Pin >= 0 && j - Pin < n && j - Pin < xT)) {
-          v = xr[j - Pin];
-          if (sa) v = snake(v, a_, b_);
-        }
-      }
-      if (BC_DOK(j >= 0 && j < W && row < rows)) wr[j] = v;
-      if (j >= keep && j < S && BC_DOK(ctx_out != nullptr && j - keep >= 0 && j - keep < Pout))
-        ctx_out[(long long)row * Pout + (j - keep)] = v;
-    }
-  }
+  return launch_window(WinDense<true>{ctx, ctx_out, P, n, P}, x, xbs, xT, sa, sb, win, C, W, rows, st);
 }
 
 int stream_window_la_launch(const float* x, long long xbs, long long xT, const float* ctx, const float* sa,
@@ -291,49 +352,7 @@ int stream_window_la_launch(const float* x, long long xbs, long long xT, const f
   if (W < 1 || Pout > S) return BC_ERR_ARG;
   if (rows > 0x7fffffffLL || W > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
   if (rows == 0) return BC_OK;
-  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
-  hipLaunchKernelGGL(stream_window_la_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, ctx, sa, sb, win, ctx_out, C, n,
-                     Pin, R, Pout, (int)rows);
-  BC_CHECK_LAUNCH();
-  return BC_OK;
-}
-
-// Streaming session pool (streaming.py StreamPool): stream_window_kernel with the contexts of many independent
-// sessions in a pool[pool_rows][C][P] and two device index arrays: entry b of a push reads its context from pool row
-// src[b] (src[b] < 0: a fresh session, zeros) and stores its next context to pool row dst[b] (dst[b] < 0: not stored,
-// the padding entries of a graph replay).  Same window, same snake(), same strided x.
-// IN-PLACE HAZARD: with n < P, context element i of a row is read by the thread that writes window column i and
-// overwritten by the thread at column n + i, which may sit in another workgroup, so a row must never be read and
-// written in one launch.  The HOST guarantees it: the src and dst row sets of a launch are disjoint and dst holds no
-// row twice (StreamPool's ping-pong rows 2s / 2s + 1 per session); the kernel cannot check it.
-// Same 2-D grid and 32-bit row arithmetic as stream_window_kernel.
-__global__ void __launch_bounds__(256) stream_window_slots_kernel(const float* __restrict__ x, long long xbs, long long xT,
-                                                                  float* pool, const int* __restrict__ src,
-                                                                  const int* __restrict__ dst, const float* __restrict__ sa,
-                                                                  const float* __restrict__ sb, float* __restrict__ win,
-                                                                  int C, int n, int P, int rows, int pool_rows) {
-  const int W = P + n;
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int b = row / C, c = row - b * C;
-    const int s = src[b], d = dst[b];
-    const float* xr = x + (long long)b * xbs + (long long)c * xT;
-    float* wr = win + (long long)row * W;
-    // (the slot values come from device memory: the debug build checks them against the pool, a bad one is skipped)
-    const float* cr = (s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * P : nullptr;
-    float* nr = (d >= 0 && BC_DOK(d < pool_rows)) ? pool + ((long long)d * C + c) * P : nullptr;
-    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
-      float v;
-      if (j < P) {
-        v = cr ? cr[j] : 0.f;
-      } else {
-        v = xr[j - P];
-        if (sa) v = snake(v, a_, b_);
-      }
-      wr[j] = v;
-      if (j >= n && nr) nr[j - n] = v;
-    }
-  }
+  return launch_window(WinDense<false>{ctx, ctx_out, Pin, n, Pout}, x, xbs, xT, sa, sb, win, C, W, rows, st);
 }
 
 int stream_window_slots_launch(const float* x, long long xbs, long long xT, float* pool, const int* src, const int* dst,
@@ -344,49 +363,12 @@ int stream_window_slots_launch(const float* x, long long xbs, long long xT, floa
   const long long rows = (long long)B * C, W = (long long)P + n;
   if (rows > 0x7fffffffLL || W > 0x7fffffffLL || (long long)pool_rows * C > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
   if (rows == 0) return BC_OK;
-  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
-  hipLaunchKernelGGL(stream_window_slots_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, pool, src, dst, sa, sb, win,
-                     C, n, P, (int)rows, pool_rows);
-  BC_CHECK_LAUNCH();
-  return BC_OK;
+  return launch_window(WinSlots<false>{pool, src, dst, nullptr, 1, P, P, n, pool_rows}, x, xbs, xT, sa, sb, win, C, W,
+                       rows, st);
 }
 
-// A chunk length per entry (StreamPool.push(..., hops=)): entry b delivers L = clamp(lens[b] * unit, 0, n) columns,
-// left-aligned in its row of x (lens in hops, unit = this stage's columns per hop).  Its window is [context | chunk[:L]]
-// followed by zeros up to P + n, so every later stage's values past the entry's end are functions of zeros, biases and
-// Snake (finite, and no other entry's business: columns are independent downstream); x is never read at or past L
-// (it may hold NaN there); the next context is the last P columns of [context | chunk[:L]], win[L + i], which with
-// L < P reaches back into the old context.  lens[b] * unit == n for every b is stream_window_slots_kernel bit for bit.
-// Same src / dst contract, same grid.
-__global__ void __launch_bounds__(256) stream_window_slots_lens_kernel(
-    const float* __restrict__ x, long long xbs, long long xT, float* pool, const int* __restrict__ src,
-    const int* __restrict__ dst, const int* __restrict__ lens, int unit, const float* __restrict__ sa,
-    const float* __restrict__ sb, float* __restrict__ win, int C, int n, int P, int rows, int pool_rows) {
-  const int W = P + n;
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int b = row / C, c = row - b * C;
-    const int s = src[b], d = dst[b];
-    const long long want = (long long)lens[b] * unit;
-    const int L = want < 0 ? 0 : want > n ? n : (int)want;
-    const float* xr = x + (long long)b * xbs + (long long)c * xT;
-    float* wr = win + (long long)row * W;
-    const float* cr = (s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * P : nullptr;
-    float* nr = (d >= 0 && BC_DOK(d < pool_rows)) ? pool + ((long long)d * C + c) * P : nullptr;
-    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
-      float v = 0.f;
-      if (j < P) {
-        v = cr ? cr[j] : 0.f;
-      } else if (j - P < L) {
-        v = xr[j - P];
-        if (sa) v = snake(v, a_, b_);
-      }
-      wr[j] = v;
-      if (nr && j >= L && j < L + P && BC_DOK(j - L >= 0 && j - L < P)) nr[j - L] = v;
-    }
-  }
-}
-
+// A chunk length per entry (StreamPool.push(..., hops=)): lens in hops, unit = this stage's columns per hop.
+// lens[b] * unit == n for every b is bc_stream_window_slots bit for bit.
 int stream_window_slots_lens_launch(const float* x, long long xbs, long long xT, float* pool, const int* src,
                                     const int* dst, const int* lens, int unit, const float* sa, const float* sb,
                                     float* win, int B, int C, int n, int P, int pool_rows, hipStream_t st) {
@@ -396,57 +378,8 @@ int stream_window_slots_lens_launch(const float* x, long long xbs, long long xT,
   const long long rows = (long long)B * C, W = (long long)P + n;
   if (rows > 0x7fffffffLL || W > 0x7fffffffLL || (long long)pool_rows * C > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
   if (rows == 0) return BC_OK;
-  const int gx = (int)std::min<long long>((W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
-  hipLaunchKernelGGL(stream_window_slots_lens_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, pool, src, dst, lens,
-                     unit, sa, sb, win, C, n, P, (int)rows, pool_rows);
-  BC_CHECK_LAUNCH();
-  return BC_OK;
-}
-
-// Look-ahead session pool (streaming.py LookaheadPool): stream_window_la_kernel's window (carry in and
-// carry out of different lengths, zeros behind) over stream_window_slots_lens_kernel's pool rows (src / dst, a length
-// per entry), plus an input offset per entry.  Every stage's window is left-aligned and ragged: entry b's row is
-// [its cin[b] carried columns | its n[b] new columns, read from x at column xoff[b] on | zeros up to W], and the
-// carry it stores is cout[b] columns of that row from column keep[b] on.  A stage's right zero padding at the flush
-// and the zero tail behind a short entry are the same literal zeros, so flushing and pushing entries share a launch.
-// pool is [pool_rows][C][Pmax]: Pmax is the row pitch, an entry uses the first cin / cout columns of its rows.
-// src[b] < 0 reads the cin[b] carried columns as zeros (a fresh session: its left zero padding); dst[b] < 0 or
-// cout[b] == 0 stores nothing.  cin and cout are clamped to [0, Pmax], xoff to [0, xn] and n to [0, min(W - cin,
-// xn - xoff)], so no index array can take an access out of x, win or a pool row; x is never read outside
-// [xoff, xoff + n).  Same src / dst contract (the HOST keeps the two row sets disjoint), same snake(), same strided x,
-// same 2-D grid and one float per lane as the neighbours (Pin = 6, 18, 54: no 16-byte path fits, see above).
-__global__ void __launch_bounds__(256) stream_window_slots_la_kernel(
-    const float* __restrict__ x, long long xbs, long long xT, int xn, float* pool, const int* __restrict__ src,
-    const int* __restrict__ dst, const int* __restrict__ cin, const int* __restrict__ nnew,
-    const int* __restrict__ xoff, const int* __restrict__ keep, const int* __restrict__ cout,
-    const float* __restrict__ sa, const float* __restrict__ sb, float* __restrict__ win, int C, int W, int Pmax, int rows,
-    int pool_rows) {
-  for (int row = blockIdx.y; row < rows; row += gridDim.y) {
-    const int b = row / C, c = row - b * C;
-    const int s = src[b], d = dst[b], k = keep[b];
-    const int ci = min(max(cin[b], 0), Pmax), co = min(max(cout[b], 0), Pmax);
-    const int xo = min(max(xoff[b], 0), xn);
-    const int n = min(max(nnew[b], 0), min(W - ci, xn - xo));  // (W - ci < 0: no new column, the carry fills the row)
-    const int S = ci + n;
-    const float* xr = x + (long long)b * xbs + (long long)c * xT + xo;
-    float* wr = win + (long long)row * W;
-    const float* cr = (s >= 0 && BC_DOK(s < pool_rows)) ? pool + ((long long)s * C + c) * Pmax : nullptr;
-    float* nr = (d >= 0 && co > 0 && BC_DOK(d < pool_rows)) ? pool + ((long long)d * C + c) * Pmax : nullptr;
-    const float a_ = sa ? sa[c] : 0.f, b_ = sa ? sb[c] : 0.f;
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < W; j += gridDim.x * blockDim.x) {
-      float v = 0.f;
-      if (j < ci) {
-        if (cr && BC_DOK(j >= 0 && j < Pmax)) v = cr[j];
-      } else if (j < S) {
-        if (BC_DOK(j - ci >= 0 && xo + (j - ci) < xn && xo + (j - ci) < xT)) {
-          v = xr[j - ci];
-          if (sa) v = snake(v, a_, b_);
-        }
-      }
-      if (BC_DOK(j >= 0 && j < W && row < rows)) wr[j] = v;
-      if (nr && j >= k && j - k < co && BC_DOK(j - k >= 0 && j - k < Pmax && j < S)) nr[j - k] = v;
-    }
-  }
+  return launch_window(WinSlots<true>{pool, src, dst, lens, unit, P, P, n, pool_rows}, x, xbs, xT, sa, sb, win, C, W,
+                       rows, st);
 }
 
 int stream_window_slots_la_launch(const float* x, long long xbs, long long xT, int xn, float* pool, const int* src,
@@ -460,11 +393,8 @@ int stream_window_slots_la_launch(const float* x, long long xbs, long long xT, i
   const long long rows = (long long)B * C;
   if (rows > 0x7fffffffLL || (long long)pool_rows * C > 0x7fffffffLL) return BC_ERR_UNSUPPORTED;
   if (rows == 0) return BC_OK;
-  const int gx = (int)std::min<long long>(((long long)W + 255) / 256, 1024), gy = (int)std::min<long long>(rows, 65535);
-  hipLaunchKernelGGL(stream_window_slots_la_kernel, dim3(gx, gy), dim3(256), 0, st, x, xbs, xT, xn, pool, src, dst, cin,
-                     nnew, xoff, keep, cout, sa, sb, win, C, W, Pmax, (int)rows, pool_rows);
-  BC_CHECK_LAUNCH();
-  return BC_OK;
+  return launch_window(WinSlotsLa{pool, src, dst, cin, nnew, xoff, keep, cout, W, Pmax, Pmax, xn, pool_rows}, x, xbs, xT,
+                       sa, sb, win, C, W, rows, st);
 }
 
 // The carried ResLSTM state of a session pool: bc_reslstm_fwd_state takes dense [num_layers][H][B] (unit-major) h0 / c0

@@ -411,49 +411,32 @@ Tensor vq2emb_ct(const Tensor& idx, const Tensor& cbs, const Tensor& w_out, cons
   return out;
 }
 
-std::vector<Tensor> stream_window(const Tensor& x, const optional<Tensor>& ctx, const optional<Tensor>& a,
-                                  const optional<Tensor>& ib, int64_t P) {
-  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
-  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && x.stride(2) == 1,
-                    "bigcodec::stream_window: x must be a (B, C, n) float32 tensor with unit time stride");
-  const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
-  TORCH_CHECK_VALUE(P >= 0 && n >= 1, "bigcodec::stream_window: P >= 0 and a non-empty chunk");
-  check_coeffs(a, ib, C, "stream_window");
-  if (ctx) TORCH_CHECK_VALUE(ctx->sizes() == at::IntArrayRef({B, C, P}), "bigcodec::stream_window: ctx must be (B, C, P)");
-  auto win = at::empty({B, C, P + n}, x.options());
-  auto nctx = at::empty({B, C, P}, x.options());
-  ok(bc_stream_window(x.data_ptr<float>(), B > 1 ? x.stride(0) : C * x.stride(1), C > 1 ? x.stride(1) : n,
-                      optf(x, ctx, "ctx"), optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"), win.data_ptr<float>(),
-                      nctx.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(P, "P"), stream_of(x)),
-     "bc_stream_window");
-  return {win, nctx};
-}
+// ---- the five stream_window ops (elementwise.hip window_kernel) share their view of x and of the pool ----------------
+struct WindowX {
+  int64_t B, C, n, xbs, xT;
+  const float* p;  // null without columns
+};
 
-// ---- stream_window_la: the window of a look-ahead stream's lazy stage (carry in / carry out of different lengths,
-// right zeros at the flush); an empty x (n == 0) is a flush without new input -------------------------------------
-std::vector<Tensor> stream_window_la(const Tensor& x, const optional<Tensor>& ctx, const optional<Tensor>& a,
-                                     const optional<Tensor>& ib, int64_t Pin, int64_t R, int64_t Pout) {
+// x as (B, C, n) float32 with unit time stride, maybe a strided view; may_be_empty: no columns at all is a flush
+// without new input (stream_window_la, stream_window_slots_la_)
+WindowX window_x(const Tensor& x, const char* op, bool may_be_empty) {
   TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
-  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && (x.size(2) == 0 || x.stride(2) == 1),
-                    "bigcodec::stream_window_la: x must be a (B, C, n) float32 tensor with unit time stride");
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && ((may_be_empty && x.size(2) == 0) || x.stride(2) == 1),
+                    "bigcodec::", op, ": x must be a (B, C, n) float32 tensor with unit time stride");
   const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
-  TORCH_CHECK_VALUE(Pin >= 0 && R >= 0 && Pout >= 0 && Pin + n + R >= 1 && Pout <= Pin + n,
-                    "bigcodec::stream_window_la: Pin, R, Pout >= 0, a non-empty window and Pout <= Pin + n");
-  check_coeffs(a, ib, C, "stream_window_la");
-  if (ctx)
-    TORCH_CHECK_VALUE(ctx->sizes() == at::IntArrayRef({B, C, Pin}), "bigcodec::stream_window_la: ctx must be (B, C, Pin)");
-  auto win = at::empty({B, C, Pin + n + R}, x.options());
-  auto nctx = at::empty({B, C, Pout}, x.options());
   const int64_t xT = n && C > 1 ? x.stride(1) : n, xbs = n && B > 1 ? x.stride(0) : C * xT;  // (size-1 dims: any stride)
-  ok(bc_stream_window_la(n ? x.data_ptr<float>() : nullptr, xbs, xT, optf(x, ctx, "ctx"), optf(x, a, "alpha_exp"),
-                         optf(x, ib, "inv_beta"), win.data_ptr<float>(), Pout ? nctx.data_ptr<float>() : nullptr,
-                         i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(Pin, "Pin"), i32(R, "R"), i32(Pout, "Pout"),
-                         stream_of(x)),
-     "bc_stream_window_la");
-  return {win, nctx};
+  return {B, C, n, xbs, xT, n ? x.data_ptr<float>() : nullptr};
 }
 
-// ---- the streaming session pool: stream_window over pool rows, and the ResLSTM state gather / scatter ----------
+// pool as (rows, C, P); P < 0: any row pitch Pmax >= 1
+float* window_pool(const Tensor& x, const Tensor& pool, int64_t C, int64_t P, const char* op) {
+  dev(pool, "pool");
+  same_device(x, pool, "pool");
+  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && (P < 0 ? pool.size(2) >= 1 : pool.size(2) == P),
+                    "bigcodec::", op, ": pool must be (rows, C, ", P < 0 ? "Pmax), Pmax >= 1" : "P)");
+  return pool.data_ptr<float>();
+}
+
 const int* slots(const Tensor& ref, const Tensor& t, int64_t B, const char* op, const char* name) {
   dev(t, name, at::kInt);
   same_device(ref, t, name);
@@ -461,24 +444,52 @@ const int* slots(const Tensor& ref, const Tensor& t, int64_t B, const char* op, 
   return t.data_ptr<int>();
 }
 
+std::vector<Tensor> stream_window(const Tensor& x, const optional<Tensor>& ctx, const optional<Tensor>& a,
+                                  const optional<Tensor>& ib, int64_t P) {
+  const auto [B, C, n, xbs, xT, px] = window_x(x, "stream_window", false);
+  TORCH_CHECK_VALUE(P >= 0 && n >= 1, "bigcodec::stream_window: P >= 0 and a non-empty chunk");
+  check_coeffs(a, ib, C, "stream_window");
+  if (ctx) TORCH_CHECK_VALUE(ctx->sizes() == at::IntArrayRef({B, C, P}), "bigcodec::stream_window: ctx must be (B, C, P)");
+  auto win = at::empty({B, C, P + n}, x.options());
+  auto nctx = at::empty({B, C, P}, x.options());
+  ok(bc_stream_window(px, xbs, xT, optf(x, ctx, "ctx"), optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
+                      win.data_ptr<float>(), nctx.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(P, "P"),
+                      stream_of(x)),
+     "bc_stream_window");
+  return {win, nctx};
+}
+
+// the window of a look-ahead stream's lazy stage: carry in / carry out of different lengths, right zeros at the flush
+std::vector<Tensor> stream_window_la(const Tensor& x, const optional<Tensor>& ctx, const optional<Tensor>& a,
+                                     const optional<Tensor>& ib, int64_t Pin, int64_t R, int64_t Pout) {
+  const auto [B, C, n, xbs, xT, px] = window_x(x, "stream_window_la", true);
+  TORCH_CHECK_VALUE(Pin >= 0 && R >= 0 && Pout >= 0 && Pin + n + R >= 1 && Pout <= Pin + n,
+                    "bigcodec::stream_window_la: Pin, R, Pout >= 0, a non-empty window and Pout <= Pin + n");
+  check_coeffs(a, ib, C, "stream_window_la");
+  if (ctx)
+    TORCH_CHECK_VALUE(ctx->sizes() == at::IntArrayRef({B, C, Pin}), "bigcodec::stream_window_la: ctx must be (B, C, Pin)");
+  auto win = at::empty({B, C, Pin + n + R}, x.options());
+  auto nctx = at::empty({B, C, Pout}, x.options());
+  ok(bc_stream_window_la(px, xbs, xT, optf(x, ctx, "ctx"), optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
+                         win.data_ptr<float>(), Pout ? nctx.data_ptr<float>() : nullptr, i32(B, "B"), i32(C, "C"),
+                         i32(n, "n"), i32(Pin, "Pin"), i32(R, "R"), i32(Pout, "Pout"), stream_of(x)),
+     "bc_stream_window_la");
+  return {win, nctx};
+}
+
+// the streaming session pool: the window over pool rows
 Tensor stream_window_slots_(const Tensor& x, const Tensor& pool, const Tensor& src, const Tensor& dst,
                             const optional<Tensor>& a, const optional<Tensor>& ib, int64_t P) {
-  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
-  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && x.stride(2) == 1,
-                    "bigcodec::stream_window_slots_: x must be a (B, C, n) float32 tensor with unit time stride");
-  const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
+  const char* op = "stream_window_slots_";
+  const auto [B, C, n, xbs, xT, px] = window_x(x, op, false);
   TORCH_CHECK_VALUE(P >= 1 && n >= 1, "bigcodec::stream_window_slots_: P >= 1 and a non-empty chunk");
-  check_coeffs(a, ib, C, "stream_window_slots_");
-  dev(pool, "pool");
-  same_device(x, pool, "pool");
-  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && pool.size(2) == P,
-                    "bigcodec::stream_window_slots_: pool must be (rows, C, P)");
-  const int* ps = slots(x, src, B, "stream_window_slots_", "src");
-  const int* pd = slots(x, dst, B, "stream_window_slots_", "dst");
+  check_coeffs(a, ib, C, op);
+  float* pp = window_pool(x, pool, C, P, op);
+  const int* ps = slots(x, src, B, op, "src");
+  const int* pd = slots(x, dst, B, op, "dst");
   auto win = at::empty({B, C, P + n}, x.options());
   if (B == 0) return win;
-  ok(bc_stream_window_slots(x.data_ptr<float>(), B > 1 ? x.stride(0) : C * x.stride(1), C > 1 ? x.stride(1) : n,
-                            pool.data_ptr<float>(), ps, pd, optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
+  ok(bc_stream_window_slots(px, xbs, xT, pp, ps, pd, optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
                             win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"), i32(P, "P"),
                             i32(pool.size(0), "pool rows"), stream_of(x)),
      "bc_stream_window_slots");
@@ -488,48 +499,35 @@ Tensor stream_window_slots_(const Tensor& x, const Tensor& pool, const Tensor& s
 Tensor stream_window_slots_lens_(const Tensor& x, const Tensor& pool, const Tensor& src, const Tensor& dst,
                                  const Tensor& lens, int64_t unit, const optional<Tensor>& a, const optional<Tensor>& ib,
                                  int64_t P) {
-  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
-  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && x.stride(2) == 1,
-                    "bigcodec::stream_window_slots_lens_: x must be a (B, C, n) float32 tensor with unit time stride");
-  const int64_t B = x.size(0), C = x.size(1), n = x.size(2);
+  const char* op = "stream_window_slots_lens_";
+  const auto [B, C, n, xbs, xT, px] = window_x(x, op, false);
   TORCH_CHECK_VALUE(P >= 1 && n >= 1 && unit >= 1, "bigcodec::stream_window_slots_lens_: P >= 1, unit >= 1 and a non-empty chunk");
-  check_coeffs(a, ib, C, "stream_window_slots_lens_");
-  dev(pool, "pool");
-  same_device(x, pool, "pool");
-  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && pool.size(2) == P,
-                    "bigcodec::stream_window_slots_lens_: pool must be (rows, C, P)");
-  const int* ps = slots(x, src, B, "stream_window_slots_lens_", "src");
-  const int* pd = slots(x, dst, B, "stream_window_slots_lens_", "dst");
+  check_coeffs(a, ib, C, op);
+  float* pp = window_pool(x, pool, C, P, op);
+  const int* ps = slots(x, src, B, op, "src");
+  const int* pd = slots(x, dst, B, op, "dst");
   dev(lens, "lens", at::kInt);
   same_device(x, lens, "lens");
   TORCH_CHECK_VALUE(lens.dim() == 1 && lens.size(0) == B, "bigcodec::stream_window_slots_lens_: lens must be (", B, ",) int32, hops per entry");
-  const int* pl = lens.data_ptr<int>();
   auto win = at::empty({B, C, P + n}, x.options());
   if (B == 0) return win;
-  ok(bc_stream_window_slots_lens(x.data_ptr<float>(), B > 1 ? x.stride(0) : C * x.stride(1), C > 1 ? x.stride(1) : n,
-                                 pool.data_ptr<float>(), ps, pd, pl, i32(unit, "unit"), optf(x, a, "alpha_exp"),
+  ok(bc_stream_window_slots_lens(px, xbs, xT, pp, ps, pd, lens.data_ptr<int>(), i32(unit, "unit"), optf(x, a, "alpha_exp"),
                                  optf(x, ib, "inv_beta"), win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(n, "n"),
                                  i32(P, "P"), i32(pool.size(0), "pool rows"), stream_of(x)),
      "bc_stream_window_slots_lens");
   return win;
 }
 
-// ---- stream_window_slots_la_: the left-aligned ragged window of a look-ahead pool's stage (streaming.py LookaheadPool):
-// seven int32 (B,) device arrays per launch; x may have no columns (a push in which this stage only flushes) -------
+// the left-aligned ragged window of a look-ahead pool's stage (streaming.py LookaheadPool): seven int32 (B,) device
+// arrays per launch; x may have no columns (a push in which this stage only flushes)
 Tensor stream_window_slots_la_(const Tensor& x, const Tensor& pool, const Tensor& src, const Tensor& dst,
                                const Tensor& cin, const Tensor& n, const Tensor& xoff, const Tensor& keep,
                                const Tensor& cout, const optional<Tensor>& a, const optional<Tensor>& ib, int64_t W) {
-  TORCH_CHECK(x.is_cuda(), "bigcodec: x must be a HIP device tensor (there is no CPU path)");
-  TORCH_CHECK_VALUE(x.scalar_type() == at::kFloat && x.dim() == 3 && (x.size(2) == 0 || x.stride(2) == 1),
-                    "bigcodec::stream_window_slots_la_: x must be a (B, C, n) float32 tensor with unit time stride");
-  const int64_t B = x.size(0), C = x.size(1), xn = x.size(2);
-  TORCH_CHECK_VALUE(W >= 1, "bigcodec::stream_window_slots_la_: a non-empty window (W >= 1)");
-  check_coeffs(a, ib, C, "stream_window_slots_la_");
-  dev(pool, "pool");
-  same_device(x, pool, "pool");
-  TORCH_CHECK_VALUE(pool.dim() == 3 && pool.size(0) >= 1 && pool.size(1) == C && pool.size(2) >= 1,
-                    "bigcodec::stream_window_slots_la_: pool must be (rows, C, Pmax), Pmax >= 1");
   const char* op = "stream_window_slots_la_";
+  const auto [B, C, xn, xbs, xT, px] = window_x(x, op, true);
+  TORCH_CHECK_VALUE(W >= 1, "bigcodec::stream_window_slots_la_: a non-empty window (W >= 1)");
+  check_coeffs(a, ib, C, op);
+  float* pp = window_pool(x, pool, C, -1, op);
   const int* ps = slots(x, src, B, op, "src");
   const int* pd = slots(x, dst, B, op, "dst");
   const int* pci = slots(x, cin, B, op, "cin");
@@ -539,11 +537,9 @@ Tensor stream_window_slots_la_(const Tensor& x, const Tensor& pool, const Tensor
   const int* pco = slots(x, cout, B, op, "cout");
   auto win = at::empty({B, C, W}, x.options());
   if (B == 0) return win;
-  const int64_t xT = xn && C > 1 ? x.stride(1) : xn, xbs = xn && B > 1 ? x.stride(0) : C * xT;  // (size-1 dims: any stride)
-  ok(bc_stream_window_slots_la(xn ? x.data_ptr<float>() : nullptr, xbs, xT, i32(xn, "x columns"), pool.data_ptr<float>(),
-                               ps, pd, pci, pn, pxo, pk, pco, optf(x, a, "alpha_exp"), optf(x, ib, "inv_beta"),
-                               win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(W, "W"), i32(pool.size(2), "Pmax"),
-                               i32(pool.size(0), "pool rows"), stream_of(x)),
+  ok(bc_stream_window_slots_la(px, xbs, xT, i32(xn, "x columns"), pp, ps, pd, pci, pn, pxo, pk, pco, optf(x, a, "alpha_exp"),
+                               optf(x, ib, "inv_beta"), win.data_ptr<float>(), i32(B, "B"), i32(C, "C"), i32(W, "W"),
+                               i32(pool.size(2), "Pmax"), i32(pool.size(0), "pool rows"), stream_of(x)),
      "bc_stream_window_slots_la");
   return win;
 }

@@ -43,9 +43,14 @@ classes above keep refusing non-causal models.
 LookaheadPool is StreamPool for those models: every stage's window is left-aligned and ragged per
 session (bc_stream_window_slots_la: a carry length, a new length, an input offset and a stored carry per entry), so
 sessions in their transient, in steady state and at their flush share one batched push.
+
+One walk of the model (_walk) gives every class above its stages, and the five bc_stream_window* calls are one kernel
+(csrc/elementwise.hip window_kernel).  The two pools share their host side (_PoolHost): the slot table, the refusals of
+a push, the pinned staging of its index arrays, and the marking of its sessions when it fails.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import torch
@@ -70,6 +75,8 @@ class StreamingEncoder:
     """Wraps a causal BigCodecEncoder; `push(x (B, 1, n))` returns the latents (B, D, n / hop) of the
     chunk.  `reset()` starts a new stream.  The batch size is fixed per stream."""
 
+    _in_samples = True  # a push takes samples (a multiple of the hop); the decoder's takes frames
+
     def __init__(self, encoder):
         _refuse_global_attention(encoder)
         convs = [m for m in encoder.modules() if hasattr(m, "causal_pad")]
@@ -81,6 +88,7 @@ class StreamingEncoder:
             raise NotImplementedError("anti-aliased activations look ahead: not streamable")
         self.encoder = encoder
         self.hop = int(encoder.hop_length)
+        self.stages = _walk(encoder)
         self.reset()
 
     def reset(self):
@@ -140,26 +148,22 @@ class StreamingEncoder:
             return self._push(x)
 
     def _push(self, x) -> torch.Tensor:
-        x = _as_input(x)
-        if x.shape[-1] % self.hop:
+        """One chunk through the model's stages (_walk: the order the look-ahead classes run too)."""
+        h = x = _as_input(x)
+        if self._in_samples and x.shape[-1] % self.hop:
             raise ValueError(f"chunk of {x.shape[-1]} samples: must be a multiple of the hop ({self.hop})")
-        blk = list(self.encoder.block)
-        final_act, last_conv = blk[-2], blk[-1]
-        h = self._conv(blk[0], x)
-        for st in blk[1:-2]:
-            if isinstance(st, EncoderBlock):
-                sub = list(st.block)
-                for ru in sub[:-2]:
-                    h = self._unit(ru, h)
-                h = self._conv(sub[-1], h, act=sub[-2])
-            elif isinstance(st, ResLSTM):
-                h = self._lstm_run(st, h)
+        for st in self.stages:
+            if st.kind == "conv":
+                h = self._conv(st.module, h, act=st.act, epilogue=st.epilogue)
+            elif st.kind == "unit":
+                h = self._unit(st.module, h)
+            elif st.kind == "lstm":
+                h = self._lstm_run(st.module, h)
             else:
-                raise NotImplementedError(f"unexpected encoder stage {type(st).__name__}")
-        self.samples += x.shape[-1]
-        out = self._conv(last_conv, h, act=final_act)
+                h = self._convT(st.module, h, st.act)
+        self.samples += x.shape[-1] * (1 if self._in_samples else self.hop)
         _lib.check_status()
-        return out
+        return h
 
     def graph(self, example) -> "StreamGraph":
         """This stream's push for chunks shaped like `example`, captured once in a HIP graph (StreamGraph)."""
@@ -179,6 +183,8 @@ class StreamingDecoder(StreamingEncoder):
     The carried state: every causal conv's input context, every upsampler's last input frame, the ResLSTM's
     (h, c)."""
 
+    _in_samples = False
+
     def __init__(self, decoder):
         _refuse_global_attention(decoder)
         convs = [m for m in decoder.modules() if hasattr(m, "causal_pad")]
@@ -190,14 +196,12 @@ class StreamingDecoder(StreamingEncoder):
             raise NotImplementedError("anti-aliased activations look ahead: not streamable")
         self.decoder = decoder
         self.hop = int(decoder.hop_length)
+        self.stages = _walk(decoder)
         self.reset()
 
-    def _convT(self, wrapper, h, act):
-        conv = wrapper.conv if isinstance(wrapper, CausalConvTranspose1d) else wrapper
+    def _convT(self, conv, h, act):
         s, K = conv.stride, conv.kernel_size
-        if K % s:
-            raise NotImplementedError(f"streaming transposed conv needs kernel_size % stride == 0 (k={K}, s={s})")
-        c = K // s - 1  # input frames of history an output block needs
+        c = K // s - 1  # input frames of history an output block needs (_convT_stage: K % s == 0)
         x = self._window(id(conv), h, c, act)
         phases, _, bias, cfg = conv.prepared(x.device, conv.phase_cfg(x.shape[0], x.shape[-1]))
         # full length (n + c - 1) s + K; padding c * s crops c * s on both sides: the n * s outputs of this chunk
@@ -205,34 +209,9 @@ class StreamingDecoder(StreamingEncoder):
                                           cfg, False)
         return out[0]
 
-    def push(self, z) -> torch.Tensor:
-        self._check_mode()
-        with _lib.status_scope():
-            return self._push_dec(z)
-
     def tokens(self, codes) -> torch.Tensor:
         """codes (B, n, Nq) int64 on the device -> waveform chunk (B, 1, n * hop)."""
         return self.push(self.decoder.tokens_to_latent(codes))
-
-    def _push_dec(self, z) -> torch.Tensor:
-        z = _as_input(z)
-        m = list(self.decoder.model)
-        final_act, last_conv = m[-3], m[-2]
-        h = self._conv(m[0], z)
-        for st in m[1:-3]:
-            if isinstance(st, ResLSTM):
-                h = self._lstm_run(st, h)
-            elif isinstance(st, DecoderBlock):
-                sub = list(st.block)
-                h = self._convT(sub[1], h, sub[0])
-                for ru in sub[2:]:
-                    h = self._unit(ru, h)
-            else:
-                raise NotImplementedError(f"unexpected decoder stage {type(st).__name__}")
-        self.samples += z.shape[-1] * self.hop
-        out = self._conv(last_conv, h, act=final_act, epilogue=1)  # the decoder's nn.Tanh in the epilogue
-        _lib.check_status()
-        return out
 
     def decode(self, z, chunk: int) -> torch.Tensor:
         """Whole latent sequence through `push` in chunks of `chunk` frames (the last may be shorter)."""
@@ -286,15 +265,10 @@ def _unit_stage(ru):
     return st
 
 
-def lookahead_stages(model):
-    """The lazy stages of a BigCodecEncoder / BigCodecDecoder in flow order: one per producer of the model's own
-    per-layer length table (frame_lengths / sample_lengths with per_layer=True, rows 1 on).  Refuses what looks ahead
-    without bound: anti-aliased activations, a bidirectional ResLSTM and the Conformer-STFT family."""
-    _refuse_global_attention(model)
-    if any(getattr(m, "antialias", False) for m in model.modules()):
-        raise NotImplementedError("anti-aliased activations replicate-pad at the clip's end: not streamable")
-    if any(isinstance(m, ResLSTM) and m.lstm.bidirectional for m in model.modules()):
-        raise NotImplementedError("a bidirectional ResLSTM reads the whole clip backwards: not streamable")
+def _walk(model):
+    """The stages of a BigCodecEncoder / BigCodecDecoder in flow order: one per producer of the model's own per-layer
+    length table (frame_lengths / sample_lengths with per_layer=True, rows 1 on).  The one walk of the model: every
+    streaming class runs this list."""
     stages = []
     if hasattr(model, "tokens_to_latent"):
         m = list(model.model)
@@ -323,6 +297,17 @@ def lookahead_stages(model):
                 raise NotImplementedError(f"unexpected encoder stage {type(st).__name__}")
         stages.append(_conv_stage(blk[-1], blk[-2]))
     return stages
+
+
+def lookahead_stages(model):
+    """The lazy stages of a model (_walk).  Refuses what looks ahead without bound: anti-aliased activations, a
+    bidirectional ResLSTM and the Conformer-STFT family."""
+    _refuse_global_attention(model)
+    if any(getattr(m, "antialias", False) for m in model.modules()):
+        raise NotImplementedError("anti-aliased activations replicate-pad at the clip's end: not streamable")
+    if any(isinstance(m, ResLSTM) and m.lstm.bidirectional for m in model.modules()):
+        raise NotImplementedError("a bidirectional ResLSTM reads the whole clip backwards: not streamable")
+    return _walk(model)
 
 
 def _stage_row(st: _Stage, state, new: int, flush: bool):
@@ -728,7 +713,97 @@ class _PoolDecoder(_PoolState, StreamingDecoder):
     pass
 
 
-class StreamPool:
+class _PoolHost:
+    """The host side StreamPool and LookaheadPool share: the slot table and its session calls, every refusal of a push
+    that needs no look at the model, the pinned staging of a push's index arrays, and the rule that a push which
+    raises after its admission leaves ITS sessions undefined.  A pool sets table, decoder, hop, capacity, channels."""
+
+    _mode = None  # the precision of the pool's first push: the one its carried state belongs to
+    _pinned = _event = None
+    _chunk_hint = ""  # what a pool with a finish() adds to the refusal of a bad chunk length
+
+    # ---- sessions ------------------------------------------------------------------------------------------------
+    def close(self, sid) -> None:
+        self.table.close(sid)
+
+    def live(self):
+        """The open session ids, ascending."""
+        return self.table.live()
+
+    def samples(self, sid) -> int:
+        """Samples session `sid` has consumed (encoder pools) or produced (decoder pools) so far."""
+        self.table.check([sid], 1, allow_undefined=True)
+        return self.table.samples[sid]
+
+    # ---- pushes --------------------------------------------------------------------------------------------------
+    @property
+    def _started(self) -> bool:
+        return self._mode is not None
+
+    def _start(self) -> None:
+        if self._mode is None:
+            self._mode = _lib.precision_mode()
+
+    def _admit(self, sids, shape, flush: bool = False, most=None, channels=None):
+        """Every host-side refusal of a push (nothing is launched before it passes); returns the ids as a list.
+        flush: a finish() takes chunks of any length."""
+        sids = self.table.check(sids, most or self.capacity)
+        channels = self.channels if channels is None else channels
+        if len(shape) != 3 or shape[0] != len(sids):
+            raise ValueError(f"input of shape {tuple(shape)} for {len(sids)} sessions: row i belongs to sids[i]")
+        if channels and shape[1] != channels:
+            raise ValueError(f"input of shape {tuple(shape)}: expected {channels} channels")
+        if not flush and (shape[2] < 1 or (not self.decoder and shape[2] % self.hop)):
+            raise ValueError(f"chunk of {shape[2]} samples: must be a positive multiple of the hop ({self.hop})"
+                             + self._chunk_hint)
+        if self._mode is not None and _lib.precision_mode() != self._mode:
+            raise RuntimeError(f"precision changed ({self._mode} -> {_lib.precision_mode()}): the pool's carried state "
+                               "belongs to the mode of its first push")
+        return sids
+
+    @staticmethod
+    def _ints(values, entries: int, lo: int, hi: int, what: str):
+        """One int in [lo, hi] per entry as a list, or ValueError."""
+        values = list(values)
+        if len(values) != entries:
+            raise ValueError(f"{len(values)} {what} for {entries} sessions: entry i belongs to sids[i]")
+        for v in values:
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"{what} entry {v!r}: an int from {lo} to {hi}")
+        return values
+
+    def _admit_tokens(self, sids, codes):
+        """tokens(): codes (len(sids), n, Nq) admitted as n frames of any width; returns (sids, n)."""
+        if not self.decoder:
+            raise TypeError("tokens() needs a pool over a decoder")
+        shape = (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape
+        return self._admit(sids, shape, channels=0), shape[2]
+
+    def _stage(self, values, out, room: int = 0) -> None:
+        """`values` into the int32 device tensor `out`: pinned staging (at least `room` ints at its first use) and a
+        copy the host does not wait for (the wait on the previous copy's event has nothing left to wait for once that
+        push's status was read)."""
+        if self._pinned is None or self._pinned.numel() < len(values):
+            self._pinned = torch.empty(max(len(values), room), dtype=torch.int32, pin_memory=out.is_cuda)
+            self._event = torch.cuda.Event() if out.is_cuda else None
+        elif self._event is not None:
+            self._event.synchronize()
+        self._pinned[:len(values)] = torch.tensor(values, dtype=torch.int32)
+        out.copy_(self._pinned[:len(values)], non_blocking=True)
+        if self._event is not None:
+            self._event.record(torch.cuda.current_stream(out.device))
+
+    @contextlib.contextmanager
+    def _marking(self, sids):
+        """Launches may have been queued when anything raises in here: the state of `sids` is undefined from then on."""
+        try:
+            yield
+        except BaseException:
+            self.table.undefined.update(sids)
+            raise
+
+
+class StreamPool(_PoolHost):
     """Many independent causal streams in one batched push: a pool of per-session state on the device.
 
         pool = StreamPool(model, capacity)   # a causal BigCodecEncoder or BigCodecDecoder (StreamingEncoder's refusals)
@@ -770,24 +845,9 @@ class StreamPool:
         conv0 = _conv_of((model.model if self.decoder else model.block)[0])
         self.channels = int(conv0.in_channels)  # of a push's input: 1 (samples) or the latent width
         self._first_history = conv0.pad_left() > 0  # the first stage's window keeps a ragged input's tail out
-        self._started = False
-        self._pinned = self._event = None
 
-    # ---- sessions ------------------------------------------------------------------------------------------------
     def open(self) -> int:
         return self.table.open()
-
-    def close(self, sid) -> None:
-        self.table.close(sid)
-
-    def live(self):
-        """The open session ids, ascending."""
-        return self.table.live()
-
-    def samples(self, sid) -> int:
-        """Samples session `sid` has consumed (encoder pools) or produced (decoder pools) so far."""
-        self.table.check([sid], 1, allow_undefined=True)
-        return self.table.samples[sid]
 
     def state_bytes(self) -> int:
         """Bytes of device state the pool holds (both ping-pong rows of every slot; 0 before the first push)."""
@@ -795,20 +855,6 @@ class StreamPool:
         return sum(t.numel() * 4 for t in s._ctx.values()) + sum(t.numel() * 4 for v in s._lstm.values() for t in v)
 
     # ---- pushes --------------------------------------------------------------------------------------------------
-    def _admit(self, sids, shape, most=None, channels=None):
-        """Every host-side refusal of a push (nothing is launched before it passes); returns the ids as a list."""
-        sids = self.table.check(sids, most or self.capacity)
-        channels = self.channels if channels is None else channels
-        if len(shape) != 3 or shape[0] != len(sids):
-            raise ValueError(f"input of shape {tuple(shape)} for {len(sids)} sessions: row i belongs to sids[i]")
-        if channels and shape[1] != channels:
-            raise ValueError(f"input of shape {tuple(shape)}: expected {channels} channels")
-        if shape[2] < 1 or (not self.decoder and shape[2] % self.hop):
-            raise ValueError(f"chunk of {shape[2]} samples: must be a positive multiple of the hop ({self.hop})")
-        if self._started:
-            self._stream._check_mode()
-        return sids
-
     def _n_hops(self, n: int) -> int:
         return n if self.decoder else n // self.hop
 
@@ -816,32 +862,14 @@ class StreamPool:
         """`hops` of a push as a list of ints (None: None), or ValueError; nothing is launched before it passes."""
         if hops is None:
             return None
-        hops = list(hops)
-        if len(hops) != entries:
-            raise ValueError(f"{len(hops)} hop counts for {entries} sessions: hops[i] belongs to sids[i]")
-        for h in hops:
-            if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= n_hops:
-                raise ValueError(f"hops entry {h!r}: an int from 1 to {n_hops} (the chunk's hops)")
+        hops = self._ints(hops, entries, 1, n_hops, "hops")
         if not self._first_history:
             raise NotImplementedError("a chunk length per session needs a first stage with causal history")
         return hops
 
     def _start(self) -> None:
-        if not self._started:  # the precision the pool's state belongs to is the one of its first push
-            self._stream._mode, self._started = _lib.precision_mode(), True
-
-    def _stage(self, rows, out) -> None:
-        """`rows` (src then dst) into the device tensor `out`: pinned staging and a copy the host does not wait for
-        (the wait on the previous copy's event has nothing left to wait for once that push's status was read)."""
-        if self._pinned is None or self._pinned.numel() < len(rows):
-            self._pinned = torch.empty(max(len(rows), 4 * self.capacity), dtype=torch.int32, pin_memory=out.is_cuda)
-            self._event = torch.cuda.Event() if out.is_cuda else None
-        elif self._event is not None:
-            self._event.synchronize()
-        self._pinned[:len(rows)] = torch.tensor(rows, dtype=torch.int32)
-        out.copy_(self._pinned[:len(rows)], non_blocking=True)
-        if self._event is not None:
-            self._event.record(torch.cuda.current_stream(out.device))
+        super()._start()
+        self._stream._mode = self._mode  # (the stream checks it again in its own push)
 
     def push(self, sids, x, hops=None) -> torch.Tensor:
         sids = self._admit(sids, x.shape)
@@ -851,22 +879,20 @@ class StreamPool:
         self._start()
         s, m = self._stream, len(sids)
         try:
-            x = _as_input(x)
-            if hops is None:
-                idx = torch.empty(2 * m, dtype=torch.int32, device=x.device)
-                self._stage(src + dst, idx)
-                s._src, s._dst = idx[:m], idx[m:]
-                y = s.push(x)
-            else:  # the hops and the output lengths ride in the same staged copy as the rows
-                unit = self.hop if self.decoder else 1  # output columns per hop
-                idx = torch.empty(4 * m, dtype=torch.int32, device=x.device)
-                self._stage(src + dst + hops + [h * unit for h in hops], idx)
-                s._src, s._dst, s._hops, s._n_hops = idx[:m], idx[m:2 * m], idx[2 * m:3 * m], n_hops
-                y = s.push(x)
-                ops.load().zero_tail_(y, None, idx[3 * m:], (n_hops - min(hops)) * unit)
-        except BaseException:
-            self.table.undefined.update(sids)
-            raise
+            with self._marking(sids):
+                x = _as_input(x)
+                if hops is None:
+                    idx = torch.empty(2 * m, dtype=torch.int32, device=x.device)
+                    self._stage(src + dst, idx, 4 * self.capacity)
+                    s._src, s._dst = idx[:m], idx[m:]
+                    y = s.push(x)
+                else:  # the hops and the output lengths ride in the same staged copy as the rows
+                    unit = self.hop if self.decoder else 1  # output columns per hop
+                    idx = torch.empty(4 * m, dtype=torch.int32, device=x.device)
+                    self._stage(src + dst + hops + [h * unit for h in hops], idx, 4 * self.capacity)
+                    s._src, s._dst, s._hops, s._n_hops = idx[:m], idx[m:2 * m], idx[2 * m:3 * m], n_hops
+                    y = s.push(x)
+                    ops.load().zero_tail_(y, None, idx[3 * m:], (n_hops - min(hops)) * unit)
         finally:
             s._hops = None
         if hops is None:
@@ -878,11 +904,8 @@ class StreamPool:
     def tokens(self, sids, codes, hops=None) -> torch.Tensor:
         """codes (len(sids), n, Nq) int64 on the device -> waveform chunks (len(sids), 1, n * hop); `hops` as in push
         (the index frames past an entry's own are never decoded into its output)."""
-        if not self.decoder:
-            raise TypeError("tokens() needs a pool over a decoder")
-        shape = (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape
-        sids = self._admit(sids, shape, channels=0)
-        self._check_hops(hops, len(sids), shape[2])
+        sids, n = self._admit_tokens(sids, codes)
+        self._check_hops(hops, len(sids), n)
         return self.push(sids, self._stream.decoder.tokens_to_latent(codes), hops)
 
     def graph(self, B: int, n: int) -> "PoolGraph":
@@ -990,7 +1013,7 @@ class LookaheadSlots:
                 self.table.close(s)
 
 
-class LookaheadPool:
+class LookaheadPool(_PoolHost):
     """Many independent look-ahead streams of a NON-causal (or causal) model in one batched push: StreamPool for the
     models LookaheadEncoder / LookaheadDecoder accept.
 
@@ -1032,56 +1055,18 @@ class LookaheadPool:
         self.lookahead = lookahead_samples(model)
         self.channels = int(self.stages[0].module.in_channels)
         self._pools = {}  # stage -> its (2 * capacity, C, Pmax) carries, or the ResLSTM's two (layers, H, 2 * capacity)
-        self._mode = None  # the precision of the pool's first push
-        self._pinned = self._event = None
         self.plan = None  # the plan of the last push (tests compare its rows with lookahead_plan's)
 
-    # ---- sessions ------------------------------------------------------------------------------------------------
+    _chunk_hint = "; finish() takes any length"
+
     def open(self) -> int:
         return self.slots.open()
-
-    def close(self, sid) -> None:
-        self.table.close(sid)
-
-    def live(self):
-        """The open session ids, ascending."""
-        return self.table.live()
-
-    def samples(self, sid) -> int:
-        """Samples session `sid` has consumed (encoder pools) or produced (decoder pools) so far."""
-        self.table.check([sid], 1, allow_undefined=True)
-        return self.table.samples[sid]
 
     def state_bytes(self) -> int:
         """Bytes of device state the pool holds (both ping-pong rows of every slot; 0 before the first push)."""
         return sum(t.numel() * 4 for v in self._pools.values() for t in (v if isinstance(v, tuple) else (v,)))
 
     # ---- pushes --------------------------------------------------------------------------------------------------
-    def _admit(self, sids, shape, flush: bool, channels=None):
-        sids = self.table.check(sids, self.capacity)
-        channels = self.channels if channels is None else channels
-        if len(shape) != 3 or shape[0] != len(sids):
-            raise ValueError(f"input of shape {tuple(shape)} for {len(sids)} sessions: row i belongs to sids[i]")
-        if channels and shape[1] != channels:
-            raise ValueError(f"input of shape {tuple(shape)}: expected {channels} channels")
-        if not flush and (shape[2] < 1 or (not self.decoder and shape[2] % self.hop)):
-            raise ValueError(f"chunk of {shape[2]} samples: must be a positive multiple of the hop ({self.hop}); "
-                             "finish() takes any length")
-        if self._mode is not None and _lib.precision_mode() != self._mode:
-            raise RuntimeError(f"precision changed ({self._mode} -> {_lib.precision_mode()}): the pool's carried state "
-                               "belongs to the mode of its first push")
-        return sids
-
-    @staticmethod
-    def _ints(values, entries: int, lo: int, hi: int, what: str):
-        values = list(values)
-        if len(values) != entries:
-            raise ValueError(f"{len(values)} {what} for {entries} sessions: entry i belongs to sids[i]")
-        for v in values:
-            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-                raise ValueError(f"{what} entry {v!r}: an int from {lo} to {hi}")
-        return values
-
     def _lens(self, sids, n: int, hops):
         """The input columns per entry of a push of n columns with `hops` (StreamPool's: ints in [1, n_hops])."""
         unit = 1 if self.decoder else self.hop
@@ -1098,18 +1083,15 @@ class LookaheadPool:
         return finish
 
     def push(self, sids, x, hops=None, finish=None):
-        sids = self._admit(sids, x.shape, False)
+        sids = self._admit(sids, x.shape)
         lens = self._lens(sids, x.shape[2], hops)
         return self._run(sids, x, lens, self._flags(sids, finish))
 
     def tokens(self, sids, codes, hops=None, finish=None):
         """codes (len(sids), n, Nq) int64 on the device; `hops` as in push (the index frames past an entry's own are
         never decoded into its output)."""
-        if not self.decoder:
-            raise TypeError("tokens() needs a pool over a decoder")
-        shape = (codes.shape[0], 0, codes.shape[1]) if codes.dim() == 3 else codes.shape
-        sids = self._admit(sids, shape, False, channels=0)
-        lens = self._lens(sids, shape[2], hops)
+        sids, n = self._admit_tokens(sids, codes)
+        lens = self._lens(sids, n, hops)
         flags = self._flags(sids, finish)
         return self._run(sids, self.model.tokens_to_latent(codes), lens, flags)
 
@@ -1130,32 +1112,15 @@ class LookaheadPool:
         return self._run(sids, x, lens, [True] * len(sids))
 
     # ---- one push ------------------------------------------------------------------------------------------------
-    def _stage_copy(self, values, out) -> None:
-        """StreamPool._stage: pinned staging and a copy the host does not wait for."""
-        if self._pinned is None or self._pinned.numel() < len(values):
-            self._pinned = torch.empty(max(len(values), 8 * self.capacity * (len(self.stages) + 1)), dtype=torch.int32,
-                                       pin_memory=out.is_cuda)
-            self._event = torch.cuda.Event() if out.is_cuda else None
-        elif self._event is not None:
-            self._event.synchronize()
-        self._pinned[:len(values)] = torch.tensor(values, dtype=torch.int32)
-        out.copy_(self._pinned[:len(values)], non_blocking=True)
-        if self._event is not None:
-            self._event.record(torch.cuda.current_stream(out.device))
-
     def _run(self, sids, x, lens, flush):
         plan = self.slots.plan(sids, lens, flush)
-        if self._mode is None:
-            self._mode = _lib.precision_mode()
-        try:
+        self._start()
+        with self._marking(sids):
             if not (x.is_cuda and x.dtype == torch.float32 and (x.stride(2) == 1 or not x.shape[2])):
                 x = _as_input(x)  # (a view with unit time stride is read in place by the first window)
             with _lib.status_scope():
                 y = self._flow(plan, x)
                 _lib.check_status()
-        except BaseException:
-            self.table.undefined.update(sids)
-            raise
         self.slots.commit(plan, plan.counts if self.decoder else plan.lens)
         self.plan = plan
         return y, list(plan.counts)
@@ -1173,7 +1138,7 @@ class LookaheadPool:
         counts_at = len(values)
         values += plan.counts
         idx = torch.empty(len(values), dtype=torch.int32, device=dev)
-        self._stage_copy(values, idx)
+        self._stage(values, idx, 8 * self.capacity * (len(self.stages) + 1))
         h = x
         for j, (st, p) in enumerate(zip(self.stages, plan.stages)):
             arr = {k: idx[o:o + m] for k, o in where[j].items()}
@@ -1335,16 +1300,16 @@ class PoolGraph:
         hops = pool._check_hops(hops, len(sids), self._n_hops)
         src, dst = pool.table.plan(sids)
         m, pad = len(sids), [-1] * (B - len(sids))
-        try:
+        with pool._marking(sids):
             if hops is None:
                 graph, output, self._last = self._graph, self.output, self._status
-                pool._stage(src + pad + dst + pad, self._idx[:2 * B])
+                pool._stage(src + pad + dst + pad, self._idx[:2 * B], 4 * pool.capacity)
             else:
                 if self._ragged is None:
                     self._ragged = self._capture(True)
                 graph, output, self._last = self._ragged
                 pool._stage(src + pad + dst + pad + hops + self._padding[2 * B + m:3 * B]
-                            + [h * self._unit for h in hops] + self._padding[3 * B + m:], self._idx)
+                            + [h * self._unit for h in hops] + self._padding[3 * B + m:], self._idx, 4 * pool.capacity)
             self.input[:m].copy_(_as_input(x))
             if self._dirty > m:
                 self.input[m:self._dirty].zero_()
@@ -1352,9 +1317,6 @@ class PoolGraph:
             graph.replay()
             if check:
                 self.check()
-        except BaseException:
-            pool.table.undefined.update(sids)
-            raise
         if hops is None:
             pool.table.commit(sids, output.shape[-1] if pool.decoder else x.shape[-1])
         else:

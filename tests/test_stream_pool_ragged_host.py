@@ -11,6 +11,7 @@ import torch
 from audiotokenization_amd import _lib as L
 from audiotokenization_amd.streaming import SlotTable, StreamPool
 from helpers import build_models
+from window_ref import window_equal, window_lens
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("bc_stream_window_slots_lens", "bc_reslstm_fwd_state_lens")
@@ -187,19 +188,6 @@ def test_random_ragged_schedules_account_per_session(capacity):
 
 
 # ---- the window formula ----------------------------------------------------------------------------------------------
-def window_lens(ctx, x, L):
-    """bc_stream_window_slots_lens for one row: (win, next context) from ctx (P,), the padded chunk x (n,) and L."""
-    P, n = ctx.numel(), x.numel()
-    win = torch.cat([ctx, x[:L], torch.zeros(n - L)])
-    return win, win[L:L + P].clone()
-
-
-def window_equal(ctx, x):
-    """bc_stream_window_slots for one row: win = [ctx | x], next context = win[n:]."""
-    win = torch.cat([ctx, x])
-    return win, win[x.numel():].clone()
-
-
 @pytest.mark.parametrize("P", [1, 6, 18, 54])
 def test_ragged_pieces_carry_the_context_of_equal_length_pushes(P):
     """A session's audio pushed in ragged pieces L_1, L_2, ... (each padded with NaN to the tick's n; L < P, L == P, L
