@@ -904,8 +904,10 @@ def test_lstm_timeout_is_loud(dev):
 @pytest.mark.parametrize("D,layers,B,T", [(64, 2, 3, 37), (512, 2, 4, 50), (1536, 1, 2, 23)])
 def test_reslstm_bidirectional(dev, D, layers, B, T):
     """ResLSTM(bidirectional=True) (vq/module.py:150-152: nn.LSTM(D, D/2, bidirectional)) against torch's
-    own CPU LSTM (oracle.res_lstm): D = 64 runs the per-step kernels (H = 32), D = 512 / 1536 the
-    persistent one (H = 256 / 768) for both directions; plus the fused output Snake."""
+    own CPU LSTM (oracle.res_lstm): D = 64 and D = 1536 run the per-step kernel (H = 32 and H = 768: lstm_seq_ok
+    accepts only H / 128 in {2, 4, 8, 12}), D = 512 the persistent one (H = 256) for both directions; plus the fused
+    output Snake.  tests/test_gpu_lstm_bidir_matrix.py holds the bidirectional call to fp64 on the recurrence's own
+    output; the metric here (max |x + h|) cannot see a lost operand plane."""
     L.load().bc_lstm_status(1)
     g = torch.Generator().manual_seed(D + T)
     m = BL.ResLSTM(D, num_layers=layers, bidirectional=True)

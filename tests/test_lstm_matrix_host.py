@@ -5,7 +5,8 @@
    operands; against one that only lost the third bf16 plane of W_hh or of h (what a broken x6 split, or an h3 that lost
    its second plane, would compute) the proof is required of the precisions in lstm_ref.LOW_PLANE_PROVEN, which is
    empty, with the figures, in test_bound_discriminates.  The cell loop that computes the degraded recurrences is first
-   checked against torch.nn.LSTM in fp64.
+   checked against torch.nn.LSTM in fp64.  test_bidir_bound_discriminates is the same for the bidirectional cases,
+   whose faults can sit in five places (either direction's W_hh or h, the reverse-half columns of W_ih).
 2. The W_hh pack layouts the kernels read: x6 at H = 1024 and 1536 (tests/test_abi.py has 256 and 512), h3 at all four
    widths, and the per-step fast kernel's (lstm_pack_hh2) at H = 128 and 1024, each under the index map written out
    here from the comments in csrc/lstm_seq.hip and csrc/lstm.hip."""
@@ -14,10 +15,11 @@ import pytest
 import torch
 
 from audiotokenization_amd import _lib as L
-from lstm_ref import (FRAG_H, K, LOW_PLANE_PROVEN, SEQ_H, SHAPES, bound, cpu32, main_case, manual_lstm, planes, ref64,
-                      rel_h, state_case)
+from lstm_ref import (BIDIR_SHAPES, FRAG_H, K, LOW_PLANE_PROVEN, SEQ_H, SHAPES, bidir_case, bidir_precs, bound, cpu32,
+                      main_case, manual_lstm, planes, ref64, rel_h, rel_h_halves, state_case)
 
 CASES = [main_case(H) for H in sorted(SHAPES)] + [state_case(H) for H in SEQ_H]
+BIDIR_CASES = [bidir_case(k) for k in BIDIR_SHAPES]
 
 
 def _precs(case):
@@ -67,6 +69,41 @@ def test_bound_discriminates(case):
             assert bound(case, prec) < 0.5 * drop, (prec, bound(case, prec), err)
         else:
             assert bound(case, prec) < 0.5 * one, (prec, bound(case, prec), err)
+
+
+BIDIR_FAULTS = ("fw", "fw_r", "fh", "fh_r", "fih")  # manual_lstm's five places a bidirectional fault can sit
+
+
+@pytest.mark.parametrize("case", BIDIR_CASES, ids=lambda c: f"D{c.D}-T{c.T}")
+def test_bidir_bound_discriminates(case):
+    """The same condition for the bidirectional matrix (tests/test_gpu_lstm_bidir_matrix.py): in every precision a case's
+    GPU legs run, bound < 1/2 of the smallest error of an fp32 recurrence with a single-plane (bf16) operand, the
+    smallest taken over W_hh and h of either direction and the [H, 2H) columns of W_ih.  Measured here at B = 70: cpu32
+    4.0e-7 (D = 96) and 1.1e-6 .. 1.6e-6, the smallest single-plane error 1.4e-3 .. 3.9e-3, the smallest dropped-plane
+    error 2.2 .. 5.9 x cpu32.  No dropped-plane guarantee is asked (DESIGN.md
+    §19); the figures are printed, per place and per channel half."""
+    ref = ref64(case)
+    m64 = manual_lstm(case, torch.float64)
+    for a, b in zip(m64, ref):  # the written-out two-direction loop is torch's bidirectional LSTM
+        assert rel_h(a, b) < 1e-12
+    err, halves = {}, {}
+    for name, n in (("drop", 2), ("one", 1)):
+        for place in BIDIR_FAULTS:
+            y = manual_lstm(case, torch.float32, **{place: lambda v: planes(v, n)})[0]
+            e = rel_h_halves(y, ref[0])
+            err[f"{name}_{place}"], halves[f"{name}_{place}"] = e[0], e[1:]
+    drop = min(v for k, v in err.items() if k.startswith("drop"))
+    one = min(v for k, v in err.items() if k.startswith("one"))
+    c32 = cpu32(case)
+    print(f"bidir D {case.D} layers {case.layers} T {case.T} B {case.B} whh_scale {case.whh_scale}: max |h| "
+          f"{float(ref[0].abs().max()):.3f} cpu32 y {c32[0]:.2e} h_n {c32[1]:.2e} c_n {c32[2]:.2e} " +
+          " ".join(f"{k} {v:.2e} (fwd {halves[k][0]:.2e} rev {halves[k][1]:.2e})" for k, v in err.items()) +
+          f" drop / cpu32 {drop / max(c32):.1f}; bounds " +
+          " ".join(f"{p} {bound(case, p):.2e} (drop = {drop / bound(case, p):.2f} x bound)" for p in bidir_precs(case)))
+    assert max(c32) < drop
+    for prec in bidir_precs(case):
+        assert bound(case, prec) >= max(c32)
+        assert bound(case, prec) < 0.5 * one, (prec, bound(case, prec), err)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
