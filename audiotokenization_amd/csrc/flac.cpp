@@ -154,6 +154,18 @@ int read_residual(Bits& b, int bs, int order, int64_t* res) {
   return FLAC_OK;
 }
 
+// Restoration runs in unsigned (wrapping) arithmetic with explicit arithmetic shifts, so every input — a
+// damaged stream's residuals and coefficients included — has a defined result.  A restored sample outside
+// its subframe's range [-2^(bits-1), 2^(bits-1)) is rejected as it is restored, so it never feeds a later
+// prediction: the history stays within 33 bits and a prediction (32 taps x 15-bit coefficients) within 54.
+// No losslessly encoded stream trips the check: its restored samples are the encoder's input.
+inline bool fits(int64_t v, int bits) {  // bits 1-33
+  const int64_t lim = (int64_t)1 << (bits - 1);
+  return v >= -lim && v < lim;
+}
+
+inline int64_t asr(int64_t v, int n) { return v < 0 ? ~(~v >> n) : v >> n; }  // floor(v / 2^n), n 0-63
+
 int read_subframe(Bits& b, int bs, int bps, int64_t* s) {
   if (b.u(1) != 0) return FLAC_ECORRUPT;
   const int type = (int)b.u(6);
@@ -171,15 +183,18 @@ int read_subframe(Bits& b, int bs, int bps, int64_t* s) {
     if (order > bs) return FLAC_ECORRUPT;
     for (int i = 0; i < order; ++i) s[i] = b.s(bps);
     if (int rc = read_residual(b, bs, order, s)) return rc;
+    const uint64_t* u = reinterpret_cast<const uint64_t*>(s);
     for (int i = order; i < bs; ++i) {
-      const int64_t r = s[i];
+      uint64_t v = u[i];
       switch (order) {
         case 0: break;
-        case 1: s[i] = r + s[i - 1]; break;
-        case 2: s[i] = r + 2 * s[i - 1] - s[i - 2]; break;
-        case 3: s[i] = r + 3 * s[i - 1] - 3 * s[i - 2] + s[i - 3]; break;
-        case 4: s[i] = r + 4 * s[i - 1] - 6 * s[i - 2] + 4 * s[i - 3] - s[i - 4]; break;
+        case 1: v += u[i - 1]; break;
+        case 2: v += 2 * u[i - 1] - u[i - 2]; break;
+        case 3: v += 3 * u[i - 1] - 3 * u[i - 2] + u[i - 3]; break;
+        case 4: v += 4 * u[i - 1] - 6 * u[i - 2] + 4 * u[i - 3] - u[i - 4]; break;
       }
+      s[i] = (int64_t)v;
+      if (!fits(s[i], bps)) return FLAC_ECORRUPT;
     }
   } else if (type >= 32) {  // LPC, order 1-32
     const int order = type - 31;
@@ -189,13 +204,14 @@ int read_subframe(Bits& b, int bs, int bps, int64_t* s) {
     if (prec == 16) return FLAC_ECORRUPT;
     const int shift = (int)b.s(5);
     if (shift < 0) return FLAC_EUNSUPPORTED;
-    int64_t coef[32];
-    for (int j = 0; j < order; ++j) coef[j] = b.s(prec);
+    uint64_t coef[32];
+    for (int j = 0; j < order; ++j) coef[j] = (uint64_t)b.s(prec);
     if (int rc = read_residual(b, bs, order, s)) return rc;
     for (int i = order; i < bs; ++i) {
-      int64_t acc = 0;
-      for (int j = 0; j < order; ++j) acc += coef[j] * s[i - 1 - j];
-      s[i] += acc >> shift;
+      uint64_t acc = 0;
+      for (int j = 0; j < order; ++j) acc += coef[j] * (uint64_t)s[i - 1 - j];
+      s[i] = (int64_t)((uint64_t)s[i] + (uint64_t)asr((int64_t)acc, shift));
+      if (!fits(s[i], bps)) return FLAC_ECORRUPT;
     }
   } else {
     return FLAC_ECORRUPT;  // reserved
@@ -216,7 +232,8 @@ long long decode_all(const uint8_t* d, uint64_t n, const StreamInfo& si, bool ch
   long long done = 0;
   std::vector<int64_t> ch[8];
   while (pos + 2 <= n) {
-    if (d[pos] != 0xFF || (d[pos + 1] & 0xFC) != 0xF8) {  // not a frame start: trailing bytes (e.g. ID3) end the stream
+    // 14-bit sync and a zero reserved bit; anything else is no frame start: trailing bytes (e.g. ID3) end the stream
+    if (d[pos] != 0xFF || (d[pos + 1] & 0xFE) != 0xF8) {
       if (done == 0) return -FLAC_ECORRUPT;
       break;
     }
@@ -255,6 +272,8 @@ long long decode_all(const uint8_t* d, uint64_t n, const StreamInfo& si, bool ch
     const uint64_t hlen = b.pos >> 3;
     const uint8_t hcrc = (uint8_t)b.u(8);
     if (check_crc && crc8(d + pos, hlen) != hcrc) return -FLAC_ECRC;
+    // the caller scales and narrows by STREAMINFO's sample size: a frame of another size is not decoded
+    if (bps != si.bits) return -FLAC_EUNSUPPORTED;
     int nch;
     if (chc <= 7) nch = chc + 1;
     else if (chc <= 10) nch = 2;
@@ -277,11 +296,15 @@ long long decode_all(const uint8_t* d, uint64_t n, const StreamInfo& si, bool ch
     } else if (chc == 10) {  // mid / side
       for (int i = 0; i < bs; ++i) {
         const int64_t side = ch[1][i];
-        const int64_t mid = ((uint64_t)ch[0][i] << 1) | (side & 1);
-        ch[0][i] = (mid + side) >> 1;
-        ch[1][i] = (mid - side) >> 1;
+        const int64_t mid = (int64_t)(((uint64_t)ch[0][i] << 1) | (uint64_t)(side & 1));
+        ch[0][i] = asr(mid + side, 1);
+        ch[1][i] = asr(mid - side, 1);
       }
     }
+    if (chc >= 8)  // the subframes were in range (at most 34 bits above): the restored channels must be too
+      for (int c = 0; c < nch; ++c)
+        for (int i = 0; i < bs; ++i)
+          if (!fits(ch[c][i], bps)) return -FLAC_ECORRUPT;
     for (int c = 0; c < nch; ++c)
       for (int i = 0; i < bs; ++i)
         if (!emit(c, done + i, ch[c][i])) return -FLAC_ESPACE;

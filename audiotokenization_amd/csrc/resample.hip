@@ -22,8 +22,9 @@ namespace bc {
 constexpr int RS_BLOCK = 256;
 constexpr int RS_MAX_KERN = 32768;  // floats of filter staged in LDS (128 KiB)
 
-// LDSW: filters staged in LDS (nw * K <= RS_MAX_KERN), else read through the caches (e.g. 22050 ->
-// 24000 Hz: 160 phases x 161 taps).
+// LDSW: filters staged in LDS (nw * K <= RS_MAX_KERN; 22050 -> 24000 Hz, 160 phases x 161 taps, still fits
+// with 103 040 bytes), else read through the caches (e.g. 44100 -> 16000 Hz: 160 phases x 475 taps, and
+// 22050 -> 16000 Hz: 320 x 459).
 template <bool LDSW>
 __global__ void __launch_bounds__(RS_BLOCK) resample_sinc_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                  const float* __restrict__ kern, long long Lin,

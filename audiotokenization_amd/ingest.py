@@ -55,9 +55,11 @@ def read_wav(path: str) -> Tuple[np.ndarray, int]:
     if fmt is None or pcm is None or len(fmt) < 16:
         raise ValueError(f"{path}: missing fmt or data chunk")
     tag, channels, rate, _, align, bits = struct.unpack("<HHIIHH", fmt[:16])
-    if tag == 0xFFFE and len(fmt) >= 26:  # WAVE_FORMAT_EXTENSIBLE: the sub-format's first two bytes
+    if tag == 0xFFFE:  # WAVE_FORMAT_EXTENSIBLE: the sub-format's first two bytes
+        if len(fmt) < 26:
+            raise ValueError(f"{path}: WAVE_FORMAT_EXTENSIBLE fmt chunk of {len(fmt)} bytes")
         tag = struct.unpack("<H", fmt[24:26])[0]
-    if channels < 1 or align != channels * ((bits + 7) // 8):
+    if channels < 1 or bits < 1 or align < 1 or align != channels * ((bits + 7) // 8):
         raise ValueError(f"{path}: inconsistent fmt chunk")
     n = len(pcm) // align
     raw = pcm[: n * align]
@@ -84,6 +86,13 @@ _FLAC_ERR = {1: "bad argument", 2: "not a FLAC stream or corrupt", 3: "unsupport
              4: "CRC mismatch", 5: "more samples than STREAMINFO announced"}
 
 
+def flac_max_samples(nbytes: int) -> int:
+    """An upper bound on the samples per channel that `nbytes` of FLAC stream can hold: a frame carries at most
+    65 536 samples and is never shorter than its fixed fields (sync and codes 4 bytes, coded number 1, CRC-8 1,
+    CRC-16 2).  read_flac sizes no buffer beyond it, whatever STREAMINFO announces."""
+    return 65536 * (nbytes // 8)
+
+
 def read_flac(path: str, data: bytes = None, check_crc: bool = True, as_int: bool = False) -> Tuple[np.ndarray, int]:
     """(waveform (C, T), sample_rate) of a FLAC file through bc_flac_decode (host decoder in
     libbigcodec_hip.so): float32 = sample / 2^(bits - 1) as soundfile.SoundFile(path).read(dtype='float32',
@@ -98,12 +107,15 @@ def read_flac(path: str, data: bytes = None, check_crc: bool = True, as_int: boo
                           ctypes_ref(total))
     if rc:
         raise ValueError(f"{path}: {_FLAC_ERR.get(rc, rc)}")
-    cap = int(total.value) if total.value > 0 else max(4096, len(data))
+    bound = flac_max_samples(len(data))
+    if total.value > bound:
+        raise ValueError(f"{path}: STREAMINFO announces {total.value} samples, more than {len(data)} bytes can hold")
+    cap = int(total.value) if total.value > 0 else min(max(4096, len(data)), bound)
     while True:
         out = np.empty((ch.value, cap), dtype=np.int32 if as_int else np.float32)
         n = lib.bc_flac_decode(buf.ctypes.data, len(data), out.ctypes.data, int(as_int), cap, int(check_crc))
-        if n == -5 and total.value <= 0:  # unknown length: grow and decode again
-            cap *= 4
+        if n == -5 and total.value <= 0 and cap < bound:  # unknown length: grow and decode again
+            cap = min(cap * 4, bound)
             continue
         if n < 0:
             raise ValueError(f"{path}: {_FLAC_ERR.get(-n, n)}")

@@ -90,6 +90,143 @@ def test_read_pcm16_wavs_like_wave_module(tmp_path):
         assert np.array_equal(x[0], x16.astype(np.float32) / 32768.0)
 
 
+def _riff(*chunks, size=None):
+    """A RIFF/WAVE file of (id, body[, claimed size]) chunks, each padded to an even length as RIFF asks."""
+    body = b"WAVE"
+    for cid, payload, *claimed in chunks:
+        body += cid + struct.pack("<I", claimed[0] if claimed else len(payload)) + payload + b"\0" * (len(payload) & 1)
+    return b"RIFF" + struct.pack("<I", len(body) if size is None else size) + body
+
+
+def _fmt(tag=1, channels=1, rate=16000, bits=16, align=None, extra=b""):
+    align = channels * ((bits + 7) // 8) if align is None else align
+    return struct.pack("<HHIIHH", tag, channels, rate, rate * align, align, bits) + extra
+
+
+_PCM = np.arange(-6, 6, dtype="<i2").tobytes()  # 12 samples
+MALFORMED_WAVS = {
+    "bits = 0": _riff((b"fmt ", _fmt(bits=0, align=0)), (b"data", _PCM)),
+    "bits = 0, align = 2": _riff((b"fmt ", _fmt(bits=0, align=2)), (b"data", _PCM)),
+    "align = 0": _riff((b"fmt ", _fmt(align=0)), (b"data", _PCM)),
+    "align is not channels * bytes": _riff((b"fmt ", _fmt(channels=2, align=3)), (b"data", _PCM)),
+    "align of one channel for two": _riff((b"fmt ", _fmt(channels=2, align=2)), (b"data", _PCM)),
+    "channels = 0": _riff((b"fmt ", _fmt(channels=0, align=2)), (b"data", _PCM)),
+    "channels = 0, align = 0": _riff((b"fmt ", _fmt(channels=0, align=0)), (b"data", _PCM)),
+    "fmt chunk of 14 bytes": _riff((b"fmt ", _fmt()[:14]), (b"data", _PCM)),
+    "fmt chunk of 0 bytes": _riff((b"fmt ", b""), (b"data", _PCM)),
+    "fmt chunk cut off by the end of the file": _riff((b"data", _PCM), (b"fmt ", _fmt()[:10], 16)),
+    "no data chunk": _riff((b"fmt ", _fmt()), (b"LIST", b"INFOxx")),
+    "no fmt chunk": _riff((b"data", _PCM)),
+    "no chunk at all": _riff(),
+    "extensible header of 24 bytes": _riff((b"fmt ", _fmt(tag=0xFFFE, extra=bytes(8))), (b"data", _PCM)),
+    "extensible header of 16 bytes": _riff((b"fmt ", _fmt(tag=0xFFFE)), (b"data", _PCM)),
+    "17-bit PCM": _riff((b"fmt ", _fmt(bits=17, align=3)), (b"data", _PCM)),
+    "unknown format tag": _riff((b"fmt ", _fmt(tag=2)), (b"data", _PCM)),
+    "not WAVE": b"RIFF" + struct.pack("<I", 4) + b"AVI ",
+    "11 bytes": b"RIFF\0\0\0\0WAV",
+    "empty file": b"",
+}
+
+
+@pytest.mark.parametrize("what", list(MALFORMED_WAVS))
+def test_read_wav_rejects_malformed_headers(tmp_path, what):
+    """Every malformed header is a ValueError (or NotImplementedError for a format that is well formed but not
+    read), never a ZeroDivisionError, a struct.error or a numpy reshape error."""
+    p = tmp_path / "bad.wav"
+    p.write_bytes(MALFORMED_WAVS[what])
+    with pytest.raises((ValueError, NotImplementedError)) as e:
+        ingest.read_wav(str(p))
+    assert type(e.value) in (ValueError, NotImplementedError), type(e.value)  # no subclass from numpy or struct
+    assert "bad.wav" in str(e.value)
+
+
+def test_read_wav_chunk_layouts(tmp_path):
+    """Layouts that are read: a data chunk whose size runs past the end of the file (the samples present are read,
+    a partial last sample frame is dropped), an odd-sized chunk before `data` (its pad byte is skipped), `fmt ` after
+    `data`, a zero-length data chunk, and a 40-byte WAVE_FORMAT_EXTENSIBLE header."""
+    want = np.arange(-6, 6, dtype=np.float32)[None] / 32768.0
+    cases = {
+        "data past the end": (_riff((b"fmt ", _fmt()), (b"data", _PCM, 1 << 20)), want),
+        "data past the end, odd": (_riff((b"fmt ", _fmt()), (b"data", _PCM + b"\x7f", 4000))[:-1], want),  # (without the pad)
+        "stereo data past the end": (_riff((b"fmt ", _fmt(channels=2)), (b"data", _PCM[:22], 400)),
+                                     want[0, :10].reshape(5, 2).T),
+        "odd chunk first": (_riff((b"fmt ", _fmt()), (b"LIST", b"INFOabc"), (b"data", _PCM)), want),
+        "odd chunks around fmt": (_riff((b"JUNK", b"x"), (b"fmt ", _fmt()), (b"fact", b"12345"), (b"data", _PCM)), want),
+        "fmt after data": (_riff((b"data", _PCM), (b"fmt ", _fmt())), want),
+        "empty data": (_riff((b"fmt ", _fmt()), (b"data", b"")), np.zeros((1, 0), np.float32)),
+        "empty stereo data": (_riff((b"fmt ", _fmt(channels=2)), (b"data", b"")), np.zeros((2, 0), np.float32)),
+        "extensible PCM16": (_riff((b"fmt ", _fmt(tag=0xFFFE, extra=struct.pack("<HHIH", 22, 16, 4, 1) + bytes(14))),
+                                   (b"data", _PCM)), want),
+        "RIFF size wrong": (_riff((b"fmt ", _fmt()), (b"data", _PCM), size=4), want),
+    }
+    for what, (data, ref) in cases.items():
+        p = tmp_path / "ok.wav"
+        p.write_bytes(data)
+        x, sr = ingest.read_wav(str(p))
+        assert sr == 16000 and x.dtype == np.float32 and x.shape == ref.shape, (what, x.shape)
+        assert np.array_equal(x, ref), what
+
+
+def _flac_header_only(total):
+    si = struct.pack(">HH", 4096, 4096) + bytes(6) + ((16000 << 44) | (0 << 41) | (15 << 36) | total).to_bytes(8, "big")
+    return b"fLaC" + bytes([0x80, 0, 0, 34]) + si + bytes(16)
+
+
+def test_read_flac_does_not_allocate_for_an_announced_total(monkeypatch):
+    """A 42-byte stream whose STREAMINFO announces 2^36 - 1 samples (256 GiB of float32) is rejected before any
+    buffer is made: read_flac bounds the announced total by what the bytes can hold (ingest.flac_max_samples)."""
+    data = _flac_header_only((1 << 36) - 1)
+    assert len(data) == 42
+    lib = ingest.L.load()
+    buf = np.frombuffer(data, np.uint8)
+    total = ingest.ctypes_longlong()
+    assert lib.bc_flac_info(buf.ctypes.data, len(data), None, None, None, ingest.ctypes_ref(total)) == 0
+    assert total.value == (1 << 36) - 1  # the header itself is well formed: the decoder would be asked to fill it
+    assert ingest.flac_max_samples(42) == 5 * 65536 and ingest.flac_max_samples(7) == 0
+
+    sizes = []
+    real_empty = np.empty
+
+    def empty(shape, *a, **k):
+        sizes.append(int(np.prod(shape)))
+        assert sizes[-1] <= 8 * 65536, f"read_flac asks for {sizes[-1]} samples for a 42-byte stream"
+        return real_empty(shape, *a, **k)
+
+    monkeypatch.setattr(ingest.np, "empty", empty)
+    for as_int in (False, True):
+        with pytest.raises(ValueError, match="more than 42 bytes can hold"):
+            ingest.read_flac("huge", data, as_int=as_int)
+    assert sizes == []
+    # one more sample than the bytes can hold is refused, the bound itself goes to the decoder (which finds no frame)
+    with pytest.raises(ValueError, match="can hold"):
+        ingest.read_flac("over", _flac_header_only(5 * 65536 + 1))
+    with pytest.raises(ValueError, match="corrupt"):
+        ingest.read_flac("at", _flac_header_only(5 * 65536))
+    assert sizes == [5 * 65536]
+
+
+def test_read_flac_unknown_total_grows_its_buffer(monkeypatch):
+    """Total unknown and more samples than max(4096, len(data)): CONSTANT subframes of 4096 samples take 12 bytes a
+    frame, so the first buffer is too small and the growth loop (x 4, bounded by flac_max_samples) runs."""
+    import flac_writer
+
+    T = 40 * 4096 + 17
+    x = np.repeat(np.arange(-20, 21, dtype=np.int64) * 700, 4096)[None, :T]
+    data = flac_writer.encode(x, 16000, 16, block_sizes=[4096], plan=lambda fi, c: dict(kind="constant"),
+                              total_known=False, extra_meta=False)
+    first = max(4096, len(data))
+    assert 16 * first < T <= 64 * first, (len(data), T)  # three growth steps
+    caps = []
+    real_empty = np.empty
+    monkeypatch.setattr(ingest.np, "empty", lambda shape, *a, **k: (caps.append(shape[1]), real_empty(shape, *a, **k))[1])
+    y, sr = ingest.read_flac("mem", data, as_int=True)
+    assert caps == [first, 4 * first, 16 * first, 64 * first]
+    assert sr == 16000 and y.shape == (1, T)
+    np.testing.assert_array_equal(y.astype(np.int64), x)
+    f, _ = ingest.read_flac("mem", data)
+    np.testing.assert_array_equal(f, (x / 32768.0).astype(np.float32))
+
+
 @pytest.mark.parametrize("orig,new", RATES)
 def test_sinc_filters_match_oracle_design(orig, new):
     k, width, o, nw = ingest.sinc_resample_kernel(orig, new)
